@@ -17,6 +17,11 @@ observing N x 5k landmarks on the same 128 control points).
 --config 3: BASELINE.json configs[3] (512 control points, 200 k residual blocks, 20 k landmarks) sharded by landmark over the N ranks,
 STRONG scaling (total work fixed). --config 2: configs[2] (stereo-inertial, order 6) on one GPU. The default (configs[1]) is the
 configuration the metric is quoted on.
+
+A plain run sets up, warms up, times --steps steps and prints the result line. --full adds the measurements that take runs of their own:
+the bearing variant of configs[1] and the CPU baseline (one host thread, then every hardware thread; --no-cpu-baseline drops it).
+--dump-outputs DIR writes what the last timed step computed (the arrays a caller of optimize() reads back) as DIR/<name>.npy in float64;
+the synthetic inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -213,13 +218,34 @@ def bearing_variant(ha, synthetic, device, steps=10):
             "ms_per_gn_iteration": 1e3 * dt / iters, "value": w.num_residual_blocks() * iters / dt, "unit": "residual_blocks/s"}
 
 
+def dump_outputs(out_dir, problem, summary, rank, inertial):
+    """--dump-outputs: what the last timed step handed its caller — the solve summary's costs and iteration records, the window state read
+    back from the device — as float64 .npy files. Rank 0 writes the replicated state; every rank writes the landmarks of its own shard."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if rank == 0:
+        arrays["costs"] = np.array([summary["initial_cost"], summary["final_cost"]], np.float64)
+        keys = ("step_is_valid", "step_is_successful", "cost", "cost_change", "gradient_max_norm", "step_norm", "relative_decrease", "radius")
+        arrays["iterations"] = np.array([[it[k] for k in keys] for it in summary["iterations"]], np.float64)
+        arrays["control_points"] = problem.control_points()
+        if inertial:
+            arrays["gravity"] = problem.gravity()
+            arrays["bias_g"], arrays["bias_a"] = problem.bias()
+    arrays["landmarks" if rank == 0 else f"landmarks_rank{rank}"] = problem.landmarks()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, default=1, choices=[1, 2, 3], help="BASELINE.json configs[i]; 1 = the metric's configuration (default)")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true", help="also the measurements that take runs of their own (bearing variant, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-worker", nargs=2, metavar=("LIB", "START"), help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_worker:
@@ -316,6 +342,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, problem, s, rank, len(window.inertial_stamps) > 0)
 
     # what the library itself says about the exchange: ranks of its RCCL communicator (ncclCommCount; 0 = hook / single shard) and the bytes
     # every rank contributes per LM iteration (one all-reduce of the reduced normal equations + one of five doubles for the decision)
@@ -426,9 +454,9 @@ def main():
         it_ms = out["ms_per_gn_iteration"]
         out["roofline_iteration"] = {"bound": "hbm", "achieved": alg_bytes / (it_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                      "frac": alg_bytes / (it_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "ms": it_ms}
-        if args.config == 1 and world == 1:  # the factor the runtime actually instantiates (abstract.cpp:243-260): same window, bearing residuals
+        if args.full and args.config == 1 and world == 1:  # the factor the runtime actually instantiates (abstract.cpp:243-260): same window, bearing residuals
             out["bearing_variant"] = bearing_variant(ha, synthetic, local_rank)
-        if not args.no_cpu_baseline and world == 1:  # reported at N = 1 only (the other ranks would idle behind rank 0's CPU run)
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N = 1 only (the other ranks would idle behind rank 0's CPU run)
             out["cpu_baseline"] = cpu_baseline(full)
             out["speedup_vs_cpu_1thread"] = out["value"] / out["cpu_baseline"]["value"]
             if out["cpu_baseline"].get("all_cores"):

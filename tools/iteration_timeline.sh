@@ -2,7 +2,7 @@
 # usage: tools/iteration_timeline.sh [config]   — start/end of every kernel of one LM iteration (rocprofv3 kernel trace), gaps and overlaps
 export TMPDIR=/tmp
 rm -rf /tmp/hs_tl
-rocprofv3 --kernel-trace --output-format csv -d /tmp/hs_tl -o t -- python bench.py --config ${1:-1} --steps 3 --warmup 2 --no-cpu-baseline > /tmp/hs_tl.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/hs_tl -o t -- python bench.py --full --config ${1:-1} --steps 3 --warmup 2 --no-cpu-baseline > /tmp/hs_tl.log 2>&1
 python - <<'PY'
 import csv, glob
 f = glob.glob("/tmp/hs_tl/**/*kernel_trace.csv", recursive=True)[0]

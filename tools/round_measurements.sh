@@ -5,8 +5,8 @@ tag=${1:-rXX}
 out=gpurun_out
 mkdir -p $out
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/${tag}_smoke.log 2>&1
-python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
-B="python bench.py --steps 40 --warmup 5 --no-cpu-baseline"
+python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+B="python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline"
 bash tools/kernel_stats.sh $out/${tag}_bench_kernel_stats.csv $B > $out/${tag}_kernel_stats.txt 2>&1
 bash tools/kernel_stats.sh $out/${tag}_config2_kernel_stats.csv python bench.py --config 2 --steps 20 --warmup 3 --no-cpu-baseline >> $out/${tag}_kernel_stats.txt 2>&1
 bash tools/kernel_stats.sh $out/${tag}_replay_kernel_stats.csv hyperslam_amd/host/replay 6.0 1 4 >> $out/${tag}_kernel_stats.txt 2>&1
