@@ -141,7 +141,34 @@ _PRODUCT_ONLY = {
     "rccl_init": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int]),
     "rccl_shutdown": (C.c_int, [C.c_void_p]),
     "exchange_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    # stereo KLT front-end (hs_tracker handle; the oracle has no counterpart)
+    "tracker_default_options": (C.c_int, [C.c_void_p]),
+    "tracker_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "tracker_destroy": (C.c_int, [C.c_void_p]),
+    "tracker_last_error": (C.c_char_p, [C.c_void_p]),
+    "tracker_build_pyramid": (C.c_int, [C.c_void_p, c_uint8_p, c_int32_p, c_uint8_p, C.POINTER(C.c_int16)]),
+    "tracker_min_eigen": (C.c_int, [C.c_void_p, c_uint8_p, C.POINTER(C.c_float)]),
+    "tracker_good_features": (C.c_int, [C.c_void_p, c_uint8_p, c_uint8_p, C.c_int, C.c_double, C.c_double, c_int32_p, C.POINTER(C.c_float)]),
+    "tracker_optical_flow": (C.c_int, [C.c_void_p, c_uint8_p, c_uint8_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), c_uint8_p, C.c_int]),
+    "tracker_process": (C.c_int, [C.c_void_p, C.c_double, c_uint8_p, c_uint8_p, c_int32_p, c_double_p, c_int32_p, C.POINTER(C.c_int64), c_int32_p,
+                                  C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "tracker_reset": (C.c_int, [C.c_void_p]),
 }
+
+
+class TrackerOptions(C.Structure):
+    _fields_ = [
+        ("max_num_tracks", C.c_int32),
+        ("min_track_separation", C.c_int32),
+        ("patch_size", C.c_int32),
+        ("num_pyramid_levels", C.c_int32),
+        ("max_iterations", C.c_int32),
+        ("reserved", C.c_int32),
+        ("min_track_quality", C.c_double),
+        ("max_track_error", C.c_double),
+        ("epsilon", C.c_double),
+        ("min_eig_threshold", C.c_double),
+    ]
 
 # every symbol include/hyperslam_hip.h declares (checked by tests/test_oracle.py::test_product_library_exports_every_declared_symbol)
 ABI_SYMBOLS = ["hs_" + n for n in list(_SIGNATURES) + list(_PRODUCT_ONLY)]

@@ -9,6 +9,7 @@
 // every evaluation entry point runs the gfx950 kernels of kernels.hpp and fails with HS_ERR_DEVICE if no GPU is usable.
 #include "host_tables.hpp"
 #include "host_launch.hpp"
+#include "tracker.hpp"
 
 /// Rows of a residual table that satisfy `drop(i)` leave; the others keep their order.
 template <class Drop>
@@ -1339,6 +1340,258 @@ int hs_sample_trajectory(hs_problem* p, int n, const double* stamps, double* pos
   if (acceleration) HIP_TRY(hipMemcpyAsync(acceleration, d_acc.p, size_t(6) * n * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return HS_OK;
+}
+
+/* ---- stereo KLT front-end (tracker.hpp, kernels_klt.hpp) ------------------------------------------------------------------------- */
+
+int hs_tracker_default_options(hs_tracker_options* o) {
+  if (!o) return HS_ERR_INVALID;
+  *o = hs_tracker_options{150, 30, 21, 3, 30, 0, 0.01, 0.5, 0.01, 1e-4};
+  return HS_OK;
+}
+
+int hs_tracker_create(int device, void* stream, int width, int height, const hs_tracker_options* o, hs_tracker** out) {
+  if (!out) return HS_ERR_INVALID;
+  *out = nullptr;
+  hs_tracker_options opt;
+  hs_tracker_default_options(&opt);
+  if (o) opt = *o;
+  if (opt.patch_size < 3 || opt.patch_size > kKltMaxPatch || opt.num_pyramid_levels < 0 || opt.num_pyramid_levels >= kKltMaxLevels ||
+      opt.max_num_tracks < 1 || opt.min_track_separation < 0 || opt.max_iterations < 1 || !(opt.epsilon >= 0) || !(opt.max_track_error > 0) ||
+      !(opt.min_track_quality > 0) || !(opt.min_eig_threshold >= 0))
+    return HS_ERR_INVALID;
+  if (width <= opt.patch_size || height <= opt.patch_size || width > 8192 || height > 8192) return HS_ERR_INVALID;
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return HS_ERR_DEVICE;
+  if (hipSetDevice(device) != hipSuccess) return HS_ERR_DEVICE;
+  hs_tracker* p = new hs_tracker();
+  p->device = device, p->w = width, p->h = height, p->o = opt;
+  if (stream) {
+    p->stream = static_cast<hipStream_t>(stream);
+  } else {
+    if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess) {
+      delete p;
+      return HS_ERR_DEVICE;
+    }
+    p->own_stream = true;
+  }
+  klt_geometry(p);
+  if (klt_alloc(p) != HS_OK || klt_reserve_points(p, opt.max_num_tracks) != HS_OK) {
+    std::fprintf(stderr, "hyperslam_hip: %s\n", p->err.c_str());
+    hs_tracker_destroy(p);
+    return HS_ERR_DEVICE;
+  }
+  *out = p;
+  return HS_OK;
+}
+
+int hs_tracker_destroy(hs_tracker* p) {
+  if (!p) return HS_OK;
+  (void)hipSetDevice(p->device);
+  if (p->stream) (void)hipStreamSynchronize(p->stream);
+  if (p->own_stream) (void)hipStreamDestroy(p->stream);
+  delete p;
+  return HS_OK;
+}
+
+const char* hs_tracker_last_error(const hs_tracker* p) { return p ? p->err.c_str() : "null handle"; }
+
+static int tracker_guard(hs_tracker* p) {
+  if (!GuardRegistry::on()) return HS_OK;
+  size_t at = 0;
+  const size_t bytes = GuardRegistry::get().check(&at);
+  if (bytes) HS_FAIL(HS_ERR_DEVICE, "HS_GUARD: a device table of " + std::to_string(bytes) + " bytes was written past its end (first overwritten guard byte at +" + std::to_string(at) + ")");
+  return HS_OK;
+}
+
+int hs_tracker_build_pyramid(hs_tracker* p, const uint8_t* image, int32_t* num_levels, uint8_t* levels, int16_t* derivatives) {
+  if (!p) return HS_ERR_INVALID;
+  if (!image || !num_levels) HS_FAIL(HS_ERR_INVALID, "hs_tracker_build_pyramid: null pointer");
+  (void)hipSetDevice(p->device);
+  int rc = klt_build(p, 4, image, -1, nullptr);
+  if (rc) return rc;
+  const KltGeom& g = p->g;
+  *num_levels = g.n_levels;
+  if (levels || derivatives) {
+    std::vector<uint8_t> im(p->level_elems);
+    std::vector<int16_t> dr(2 * p->level_elems);
+    HIP_TRY(hipMemcpyAsync(im.data(), p->img[4].p, im.size(), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(dr.data(), p->der[4].p, 2 * dr.size(), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    size_t o = 0;
+    for (int l = 0; l < g.n_levels; ++l)
+      for (int y = 0; y < g.h[l]; ++y, o += g.w[l]) {
+        const size_t src = size_t(g.off[l]) + size_t(y + g.pad) * g.stride[l] + g.pad;
+        if (levels) std::memcpy(levels + o, im.data() + src, g.w[l]);
+        if (derivatives) std::memcpy(derivatives + 2 * o, dr.data() + 2 * src, 4 * size_t(g.w[l]));
+      }
+  }
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return tracker_guard(p);
+}
+
+int hs_tracker_min_eigen(hs_tracker* p, const uint8_t* image, float* response) {
+  if (!p) return HS_ERR_INVALID;
+  if (!image || !response) HS_FAIL(HS_ERR_INVALID, "hs_tracker_min_eigen: null pointer");
+  (void)hipSetDevice(p->device);
+  const size_t px = size_t(p->w) * p->h;
+  HIP_TRY(hipMemcpyAsync(p->raw[4].p, image, px, hipMemcpyHostToDevice, p->stream));
+  k_klt_min_eigen<<<dim3((p->w + 15) / 16, (p->h + 15) / 16), 256, 0, p->stream>>>(p->raw[4].p, p->w, p->h, p->eig.p, nullptr, KltMask{});
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(response, p->eig.p, 4 * px, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return tracker_guard(p);
+}
+
+int hs_tracker_good_features(hs_tracker* p, const uint8_t* image, const uint8_t* mask, int max_corners, double quality, double min_distance,
+                             int32_t* n, float* corners) {
+  if (!p) return HS_ERR_INVALID;
+  if (!image || !n || !corners) HS_FAIL(HS_ERR_INVALID, "hs_tracker_good_features: null pointer");
+  if (!(quality > 0) || !(min_distance >= 0) || !(min_distance < 1e6)) HS_FAIL(HS_ERR_INVALID, "hs_tracker_good_features: quality must be > 0, min_distance >= 0");
+  (void)hipSetDevice(p->device);
+  const size_t px = size_t(p->w) * p->h;
+  HIP_TRY(hipMemcpyAsync(p->raw[4].p, image, px, hipMemcpyHostToDevice, p->stream));
+  KltMask m{};
+  if (mask) {
+    HIP_TRY(hipMemcpyAsync(p->mask.p, mask, px, hipMemcpyHostToDevice, p->stream));
+    m.img = p->mask.p;
+  }
+  int k = 0;
+  int rc = klt_good_features(p, 4, m, max_corners, quality, min_distance, &k);
+  if (rc) return rc;
+  *n = k;
+  if (k) HIP_TRY(hipMemcpy(corners, p->corners.p, 8 * size_t(k), hipMemcpyDeviceToHost));
+  return tracker_guard(p);
+}
+
+int hs_tracker_optical_flow(hs_tracker* p, const uint8_t* image0, const uint8_t* image1, int n, const float* points0, float* points1,
+                            uint8_t* status, int use_initial_flow) {
+  if (!p) return HS_ERR_INVALID;
+  if (n < 0 || !image0 || !image1 || (n && (!points0 || !points1 || !status))) HS_FAIL(HS_ERR_INVALID, "hs_tracker_optical_flow: bad arguments");
+  (void)hipSetDevice(p->device);
+  int rc = klt_build(p, 4, image0, 5, image1);
+  if (rc) return rc;
+  if (n) {
+    if ((rc = klt_reserve_points(p, n))) return rc;
+    HIP_TRY(hipMemcpyAsync(p->fpts[0].p, points0, 8 * size_t(n), hipMemcpyHostToDevice, p->stream));
+    if (use_initial_flow) HIP_TRY(hipMemcpyAsync(p->fpts[1].p, points1, 8 * size_t(n), hipMemcpyHostToDevice, p->stream));
+    if ((rc = klt_flow(p, {klt_pass(p, 4, 5, p->fpts[0].p, use_initial_flow ? p->fpts[1].p : nullptr, 2, n)}))) return rc;
+    HIP_TRY(hipMemcpyAsync(points1, p->fpts[2].p, 8 * size_t(n), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(status, p->fst[2].p, size_t(n), hipMemcpyDeviceToHost, p->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return tracker_guard(p);
+}
+
+int hs_tracker_reset(hs_tracker* p) {
+  if (!p) return HS_ERR_INVALID;
+  p->has_prev = false;
+  p->P0.clear(), p->P1.clear(), p->ids.clear(), p->lengths.clear();
+  p->next_id = 0;
+  return HS_OK;
+}
+
+int hs_tracker_process(hs_tracker* p, double stamp, const uint8_t* image0, const uint8_t* image1, int32_t* has_message, double* message_stamp,
+                       int32_t* n, int64_t* ids, int32_t* lengths, float* pixels0, float* pixels1) {
+  if (!p) return HS_ERR_INVALID;
+  if (!image0 || !image1 || !has_message || !n) HS_FAIL(HS_ERR_INVALID, "hs_tracker_process: null pointer");
+  (void)hipSetDevice(p->device);
+  *has_message = 0, *n = 0;
+  const int pv = p->cur, cu = 1 - p->cur;  // pairs: slots 2 pv, 2 pv + 1 (previous), 2 cu, 2 cu + 1 (current)
+  const int A0 = 2 * pv, A1 = 2 * pv + 1, B0 = 2 * cu, B1 = 2 * cu + 1;
+  int rc = klt_build(p, B0, image0, B1, image1);
+  if (rc) return rc;
+  if (!p->has_prev) {
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    p->has_prev = true, p->prev_stamp = stamp, p->cur = cu;
+    return HS_OK;
+  }
+  if (!ids || !lengths || !pixels0 || !pixels1) HS_FAIL(HS_ERR_INVALID, "hs_tracker_process: null output pointer");
+  const hs_tracker_options& o = p->o;
+  // old tracks (trackForward): prev0 -> cur0 with back-check, cur0 -> cur1 with back-check; the statuses are AND-ed per point
+  const int n_old = int(p->ids.size());
+  std::vector<float> c0, b0, c1, b1;
+  std::vector<uint8_t> s1, s2, s3, s4;
+  if (n_old) {
+    HIP_TRY(hipMemcpyAsync(p->fpts[0].p, p->P0.data(), 8 * size_t(n_old), hipMemcpyHostToDevice, p->stream));
+    if ((rc = klt_flow(p, {klt_pass(p, A0, B0, p->fpts[0].p, nullptr, 1, n_old)}))) return rc;
+    if ((rc = klt_flow(p, {klt_pass(p, B0, A0, p->fpts[1].p, p->fpts[0].p, 2, n_old), klt_pass(p, B0, B1, p->fpts[1].p, nullptr, 3, n_old)}))) return rc;
+    if ((rc = klt_flow(p, {klt_pass(p, B1, B0, p->fpts[3].p, p->fpts[1].p, 4, n_old)}))) return rc;
+    if ((rc = klt_download(p, 1, n_old, &c0, &s1)) || (rc = klt_download(p, 2, n_old, &b0, &s2)) || (rc = klt_download(p, 3, n_old, &c1, &s3)) ||
+        (rc = klt_download(p, 4, n_old, &b1, &s4)))
+      return rc;
+    HIP_TRY(hipStreamSynchronize(p->stream));
+  }
+  // trackFeatures: longest tracks first (stable), kept iff cvRound(prev position) lies outside the discs of the tracks kept before it
+  std::vector<int> order;
+  for (int i = 0; i < n_old; ++i)
+    if (klt_keep(p, s1, s2, c0, p->P0, b0, i) && klt_keep(p, s3, s4, c1, c0, b1, i)) order.push_back(i);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return p->lengths[a] > p->lengths[b]; });
+  const int r = o.min_track_separation;
+  std::vector<int> sel;
+  std::vector<float> kept;
+  for (int i : order) {
+    const int x = int(rintf(p->P0[2 * i])), y = int(rintf(p->P0[2 * i + 1]));
+    bool free = true;
+    for (size_t j = 0; j < kept.size() / 2 && free; ++j) {
+      const int dx = x - int(rintf(kept[2 * j])), dy = y - int(rintf(kept[2 * j + 1]));
+      if (dx * dx + dy * dy <= r * r) free = false;
+    }
+    if (!free) continue;
+    sel.push_back(i);
+    kept.push_back(p->P0[2 * i]), kept.push_back(p->P0[2 * i + 1]);
+  }
+  std::vector<float> M0, M1, N0, N1;
+  std::vector<int64_t> mid;
+  std::vector<int32_t> mlen;
+  for (int i : sel) {
+    M0.insert(M0.end(), {p->P0[2 * i], p->P0[2 * i + 1]}), M1.insert(M1.end(), {p->P1[2 * i], p->P1[2 * i + 1]});
+    N0.insert(N0.end(), {c0[2 * i], c0[2 * i + 1]}), N1.insert(N1.end(), {c1[2 * i], c1[2 * i + 1]});
+    mid.push_back(p->ids[i]), mlen.push_back(p->lengths[i]);
+  }
+  // selectFeatures + circularInitialization: new corners on the previous left image outside the discs, tracked six ways
+  const int want = o.max_num_tracks - int(sel.size());
+  if (want > 0) {
+    KltMask m{};
+    if (!kept.empty()) {
+      HIP_TRY(p->disc.reserve(kept.size()));
+      HIP_TRY(hipMemcpyAsync(p->disc.p, kept.data(), 4 * kept.size(), hipMemcpyHostToDevice, p->stream));
+      m.disc = p->disc.p, m.n_disc = int(kept.size() / 2), m.r = r;
+    }
+    int k = 0;
+    if ((rc = klt_good_features(p, A0, m, want, o.min_track_quality, double(o.min_track_separation), &k))) return rc;
+    if (k) {
+      const float* q = p->corners.p;
+      if ((rc = klt_flow(p, {klt_pass(p, A0, B0, q, nullptr, 6, k), klt_pass(p, A0, A1, q, nullptr, 7, k)}))) return rc;
+      if ((rc = klt_flow(p, {klt_pass(p, B0, A0, p->fpts[6].p, q, 8, k), klt_pass(p, B0, B1, p->fpts[6].p, nullptr, 9, k)}))) return rc;
+      if ((rc = klt_flow(p, {klt_pass(p, B1, B0, p->fpts[9].p, p->fpts[6].p, 10, k), klt_pass(p, A1, B1, p->fpts[7].p, p->fpts[9].p, 11, k)}))) return rc;
+      std::vector<float> nq(2 * size_t(k)), n0, q1, nb, n1, nd, circ;
+      std::vector<uint8_t> sa, se, sb, sc, sd, sf;
+      HIP_TRY(hipMemcpyAsync(nq.data(), q, 8 * size_t(k), hipMemcpyDeviceToHost, p->stream));
+      if ((rc = klt_download(p, 6, k, &n0, &sa)) || (rc = klt_download(p, 7, k, &q1, &se)) || (rc = klt_download(p, 8, k, &nb, &sb)) ||
+          (rc = klt_download(p, 9, k, &n1, &sc)) || (rc = klt_download(p, 10, k, &nd, &sd)) || (rc = klt_download(p, 11, k, &circ, &sf)))
+        return rc;
+      HIP_TRY(hipStreamSynchronize(p->stream));
+      for (int i = 0; i < k; ++i) {
+        const bool good = klt_keep(p, sa, sb, n0, nq, nb, i) && klt_keep(p, sc, sd, n1, n0, nd, i) && se[i] && sf[i] &&
+                          klt_contains(p, n1[2 * i], n1[2 * i + 1]) && klt_close(&n1[2 * i], &circ[2 * i], o.max_track_error);
+        if (!good) continue;
+        M0.insert(M0.end(), {nq[2 * i], nq[2 * i + 1]}), M1.insert(M1.end(), {q1[2 * i], q1[2 * i + 1]});
+        N0.insert(N0.end(), {n0[2 * i], n0[2 * i + 1]}), N1.insert(N1.end(), {n1[2 * i], n1[2 * i + 1]});
+        mid.push_back(p->next_id++), mlen.push_back(0);
+      }
+    }
+  }
+  const int m = int(mid.size());
+  *has_message = 1, *n = m;
+  if (message_stamp) *message_stamp = p->prev_stamp;
+  std::memcpy(ids, mid.data(), 8 * size_t(m)), std::memcpy(lengths, mlen.data(), 4 * size_t(m));
+  std::memcpy(pixels0, M0.data(), 8 * size_t(m)), std::memcpy(pixels1, M1.data(), 8 * size_t(m));
+  // the current view becomes the previous one
+  p->P0 = N0, p->P1 = N1, p->ids = mid, p->lengths = mlen;
+  for (int32_t& l : p->lengths) ++l;
+  p->prev_stamp = stamp, p->cur = cu;
+  return tracker_guard(p);
 }
 
 }  // extern "C"

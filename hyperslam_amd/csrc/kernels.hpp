@@ -33,3 +33,4 @@
 #endif
 #include "kernels_update.hpp"
 #include "kernels_aux.hpp"
+#include "kernels_klt.hpp"

@@ -301,6 +301,51 @@ int hs_manifold_minus(hs_problem* p, int kind, int ambient, int n, const double*
 /* jacobian: n x (tangent x ambient) row-major, d Minus(y, x) / dy at y = x (Manifold::MinusJacobian, wrapper.hpp:48-50). */
 int hs_manifold_minus_jacobian(hs_problem* p, int kind, int ambient, int n, const double* x, double* jacobian);
 
+/* ---- stereo KLT front-end (the step before hs_process_tracks) ------------------------------------------------------------------ */
+/* HyperSLAM's VisualFrontend (klt.cpp: callback, trackForward, trackFeatures, selectFeatures, circularInitialization) on the device:
+ * padded image pyramids, pyramidal Lucas-Kanade with a backward check, Shi-Tomasi corners with a separation mask. The arithmetic is
+ * OpenCV 4's (pyrDown, calcSharrDeriv, LKTrackerInvoker, cornerMinEigenVal, goodFeaturesToTrack) with exact integer sums (DESIGN.md,
+ * "Front-end: stereo KLT on the device"); parity with OpenCV itself is unpinned. A tracker has its own handle, stream and track-id
+ * generator and is used by one thread at a time. Images are 8-bit, row-major, width x height of the tracker, no row padding (host memory). */
+typedef struct hs_tracker hs_tracker;
+typedef struct hs_tracker_options {
+  int32_t max_num_tracks;        /* 150 */
+  int32_t min_track_separation;  /* 30 px: disc radius of the mask and minimum corner distance */
+  int32_t patch_size;            /* 21: LK window and pyramid stop size, 3..31 */
+  int32_t num_pyramid_levels;    /* 3: maxLevel, i.e. levels 0..3 (fewer where a level would not exceed the patch), 0..7 */
+  int32_t max_iterations;        /* 30 */
+  int32_t reserved;
+  double min_track_quality;      /* 0.01 */
+  double max_track_error;        /* 0.5 px: forward-backward and circular checks */
+  double epsilon;                /* 0.01: LK stops when |delta| <= epsilon */
+  double min_eig_threshold;      /* 1e-4 */
+} hs_tracker_options;
+/* The defaults above (EuRoC settings.yaml of HyperSLAM, the termination criterion of klt.cpp, OpenCV's eigenvalue threshold). */
+int hs_tracker_default_options(hs_tracker_options* o);
+/* o may be NULL (defaults); stream NULL: the tracker creates its own. HS_ERR_INVALID for bad sizes or options, HS_ERR_DEVICE without a GPU. */
+int hs_tracker_create(int device, void* stream, int width, int height, const hs_tracker_options* o, hs_tracker** out);
+int hs_tracker_destroy(hs_tracker* t);
+const char* hs_tracker_last_error(const hs_tracker* t);
+/* buildOpticalFlowPyramid + calcSharrDeriv: levels 0..num_levels-1 unpadded, one after the other (level l is w_l x h_l bytes,
+ * w_{l+1} = (w_l + 1) / 2, same for h); derivatives: int16 (dx, dy) pairs in the same order. levels / derivatives may be NULL. */
+int hs_tracker_build_pyramid(hs_tracker* t, const uint8_t* image, int32_t* num_levels, uint8_t* levels, int16_t* derivatives);
+/* cornerMinEigenVal (block 3, Sobel 3): width x height floats. */
+int hs_tracker_min_eigen(hs_tracker* t, const uint8_t* image, float* response);
+/* goodFeaturesToTrack (block 3, Shi-Tomasi): mask NULL or width x height (non-zero = allowed); corners (x, y) float pairs in acceptance
+ * order, capacity max_corners (width x height if max_corners <= 0). */
+int hs_tracker_good_features(hs_tracker* t, const uint8_t* image, const uint8_t* mask, int max_corners, double quality, double min_distance,
+                             int32_t* n, float* corners);
+/* calcOpticalFlowPyrLK image0 -> image1 with the tracker's options: points (x, y) float pairs; use_initial_flow: points1 holds the start. */
+int hs_tracker_optical_flow(hs_tracker* t, const uint8_t* image0, const uint8_t* image1, int n, const float* points0, float* points1,
+                            uint8_t* status, int use_initial_flow);
+/* VisualFrontend::callback on one complete stereo pair (left image0, right image1). Emits the PREVIOUS frame's message: has_message = 0 on
+ * the first call after create / reset; otherwise message_stamp, n tracks (capacity max_num_tracks) with ids, lengths (0 = new) and the left
+ * and right pixels in that frame, float (x, y) pairs. Pairing left and right images by stamp stays with the caller. */
+int hs_tracker_process(hs_tracker* t, double stamp, const uint8_t* image0, const uint8_t* image1, int32_t* has_message, double* message_stamp,
+                       int32_t* n, int64_t* ids, int32_t* lengths, float* pixels0, float* pixels1);
+/* Forgets the previous frame and restarts the id generator at 0. */
+int hs_tracker_reset(hs_tracker* t);
+
 #ifdef __cplusplus
 }
 #endif
