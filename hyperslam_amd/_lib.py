@@ -141,6 +141,10 @@ _PRODUCT_ONLY = {
     "rccl_init": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int]),
     "rccl_shutdown": (C.c_int, [C.c_void_p]),
     "exchange_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    # marginal covariances (the oracle has no counterpart)
+    "compute_covariance": (C.c_int, [C.c_void_p]),
+    "get_covariance": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "sample_covariance": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
     # stereo KLT front-end (hs_tracker handle; the oracle has no counterpart)
     "tracker_default_options": (C.c_int, [C.c_void_p]),
     "tracker_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -721,6 +721,134 @@ int hs_reduced_system(hs_problem* p, double radius, double* S, double* g) {
   return guard_check(p);
 }
 
+/// Marginal covariances (kernels_covariance.hpp): hs_reduced_system's launch sequence without damping, then the selected inverse of the
+/// band, the border, the unscaling and the landmark blocks — all at the device-resident point, nothing read through the cached getters.
+/// The radius is 1e300, not +inf: every build path damps with clamp(d, 1e-6, 1e32) / radius (landmarks: * inv_radius), at most 1e-268 on a
+/// Jacobi-scaled diagonal below 1 — lost in the rounding of every entry above ~1e-252, i.e. zero damping — while +inf turns the 3x3 block of a
+/// constant landmark (all zero) into 0 * inf = NaN in its factor and from there into the Y-hat rows and the reduced system. The solver's
+/// kernels are left as they are.
+int hs_compute_covariance(hs_problem* p) {
+  if (!p) return HS_ERR_INVALID;
+  if (p->has_weights()) HS_FAIL(HS_ERR_INVALID, kWeightsMessage);
+  if (p->world > 1) HS_FAIL(HS_ERR_STATE, "hs_compute_covariance: sharded handles (world > 1) are not supported");
+  p->cov_valid = false;
+  int rc = prepare(p);
+  if (rc) return rc;
+  rc = reset_state(p, 1, 1e300);
+  if (rc) return rc;
+  HS_ORDER_SWITCH(p->k, rc = launch_linearize<K>(p));
+  if (rc) return rc;
+  HS_ORDER_SWITCH(p->k, rc = launch_build<K>(p));
+  if (rc) return rc;
+  const Tables& T = p->T;
+  const int np = T.np, ncb = 6 * T.bw, nb = T.nb, n_lm = T.n_lm;
+  if (T.bw < p->k) HS_FAIL(HS_ERR_NUMERIC, "hs_compute_covariance: no residual couples the control points of one spline segment");
+  std::vector<uint8_t> cc(size_t(np) + nb);  // constant coordinates: control points (whole or rotation / translation), bias splines, gravity
+  for (int r = 0; r < np; ++r) cc[r] = p->cp_const[r / 6] || (r % 6 < 3 ? p->rot_const : p->trans_const);
+  for (int b = 0; b < nb; ++b) cc[np + b] = b < 6 * p->n_bias ? p->bias_const != 0 : p->gravity_const != 0;
+  hipStream_t s = p->stream;
+  const size_t nband = size_t(np) * ncb, npb = size_t(np) * nb + 1, nbb = size_t(nb) * nb + 1;
+  HIP_TRY(p->d_cov_const.upload(cc, s));
+  HIP_TRY(p->d_cov_U.reserve(nband));
+  HIP_TRY(p->d_cov_sig.reserve(nband));
+  HIP_TRY(p->d_cov_band.reserve(nband));
+  HIP_TRY(p->d_cov_Z.reserve(npb));
+  HIP_TRY(p->d_cov_X.reserve(npb));
+  HIP_TRY(p->d_cov_pb.reserve(npb));
+  HIP_TRY(p->d_cov_C.reserve(nbb));
+  HIP_TRY(p->d_cov_Li.reserve(nbb));
+  HIP_TRY(p->d_cov_bb.reserve(nbb));
+  HIP_TRY(p->d_cov_lm.reserve(size_t(9) * n_lm + 1));
+  HIP_TRY(p->d_cov_lm_status.reserve(size_t(n_lm) + 1));
+  HIP_TRY(p->d_cov_status.reserve(1));
+  HIP_TRY(hipMemsetAsync(p->d_cov_status.p, 0, sizeof(int), s));
+  CovBand B{T.Sb, T.Spb, T.Sbb, p->d_cov_const.p, p->d_cov_U.p, p->d_cov_sig.p, p->d_cov_Z.p, p->d_cov_X.p, p->d_cov_C.p, p->d_cov_Li.p,
+            T.scale_p, T.scale_b, p->d_cov_band.p, p->d_cov_pb.p, p->d_cov_bb.p, p->d_cov_status.p, np, ncb, nb};
+  if (ncb <= kCovLdsMaxCols) {
+    const size_t lds = cov_band_lds_doubles(true, ncb) * sizeof(double);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cov_band<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+    k_cov_band<true><<<1, kBlock, lds, s>>>(B);
+  } else {
+    k_cov_band<false><<<1, kBlock, cov_band_lds_doubles(false, ncb) * sizeof(double), s>>>(B);
+  }
+  k_cov_finish<<<T.sp.n_cp, kBlock, size_t(6) * nb * sizeof(double), s>>>(B);
+  if (n_lm) k_cov_landmarks<<<(n_lm + kBlock / 64 - 1) / (kBlock / 64), kBlock, 0, s>>>(T, p->d_cov_band.p, p->d_cov_lm.p, p->d_cov_lm_status.p);
+  HIP_TRY(hipGetLastError());
+  int status = 0;
+  std::vector<int> lm_status(n_lm);
+  HIP_TRY(hipMemcpyAsync(&status, p->d_cov_status.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (n_lm) HIP_TRY(hipMemcpyAsync(lm_status.data(), p->d_cov_lm_status.p, sizeof(int) * n_lm, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  rc = guard_check(p);
+  if (rc) return rc;
+  if (status) {
+    const int c = status - 1;
+    if (c < np)
+      HS_FAIL(HS_ERR_NUMERIC, "hs_compute_covariance: rank deficient at control point " + std::to_string(c / 6) + " (local coordinate " +
+                                  std::to_string(c % 6) + "): a free coordinate without information (gauge not fixed, or no residual touches it)");
+    HS_FAIL(HS_ERR_NUMERIC, "hs_compute_covariance: rank deficient at border unknown " + std::to_string(c - np) + " (" +
+                                (c - np < 6 * p->n_bias ? "bias control point " + std::to_string((c - np) % (3 * p->n_bias) / 3) : std::string("gravity")) + ")");
+  }
+  for (int d = 0; d < n_lm; ++d)
+    if (lm_status[d])
+      HS_FAIL(HS_ERR_NUMERIC, "hs_compute_covariance: rank deficient at landmark " + std::to_string(p->vs.table_of_dev[d]) +
+                                  " (its observations do not fix all three coordinates)");
+  p->cov_np = np, p->cov_ncb = ncb, p->cov_nb = nb, p->cov_nlm = n_lm;
+  p->cov_valid = true;
+  return HS_OK;
+}
+
+int hs_get_covariance(hs_problem* p, double* cp_blocks, double* cp_band, double* landmarks, double* border) {
+  if (!p) return HS_ERR_INVALID;
+  if (!p->cov_valid) HS_FAIL(HS_ERR_STATE, "hs_get_covariance: no covariance of the current state (call hs_compute_covariance after the last change)");
+  const int np = p->cov_np, ncb = p->cov_ncb, nb = p->cov_nb, n_lm = p->cov_nlm, n_cp = np / 6, bw = ncb / 6;
+  hipStream_t s = p->stream;
+  std::vector<double> band, lm;
+  if (cp_blocks || cp_band) {
+    band.resize(size_t(np) * ncb);
+    HIP_TRY(hipMemcpyAsync(band.data(), p->d_cov_band.p, band.size() * 8, hipMemcpyDeviceToHost, s));
+  }
+  if (landmarks && n_lm) {
+    lm.resize(size_t(9) * n_lm);
+    HIP_TRY(hipMemcpyAsync(lm.data(), p->d_cov_lm.p, lm.size() * 8, hipMemcpyDeviceToHost, s));
+  }
+  if (border && nb) HIP_TRY(hipMemcpyAsync(border, p->d_cov_bb.p, size_t(nb) * nb * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int i = 0; i < n_cp && (cp_blocks || cp_band); ++i)
+    for (int j = 0; j < bw; ++j)
+      for (int a = 0; a < 6; ++a)
+        for (int b = 0; b < 6; ++b) {
+          const double v = i + j < n_cp ? band[size_t(6 * i + a) * ncb + 6 * j + b] : 0.0;  // block (i, i + j)
+          if (cp_band) cp_band[((size_t(i) * bw + j) * 6 + a) * 6 + b] = v;
+          if (cp_blocks && j == 0) cp_blocks[(size_t(i) * 6 + a) * 6 + b] = v;
+        }
+  if (landmarks)
+    for (int d = 0; d < n_lm; ++d) std::memcpy(landmarks + size_t(9) * p->vs.table_of_dev[d], lm.data() + size_t(9) * d, 9 * sizeof(double));
+  return HS_OK;
+}
+
+int hs_sample_covariance(hs_problem* p, int n, const double* stamps, double* cov) {
+  if (!p || n < 0 || (n && (!stamps || !cov))) return HS_ERR_INVALID;
+  if (!p->cov_valid) HS_FAIL(HS_ERR_STATE, "hs_sample_covariance: no covariance of the current state (call hs_compute_covariance after the last change)");
+  if (n == 0) return HS_OK;
+  const int k = p->k, n_seg = p->n_cp - k + 1;
+  for (int i = 0; i < n; ++i) {
+    const int f = h_segment_first(stamps[i], p->t0, p->dt, k);
+    if (f < 0 || f >= n_seg) HS_FAIL(HS_ERR_INVALID, "stamp outside the valid range of the spline");
+  }
+  hipStream_t s = p->stream;
+  DBuf<double> d_st, d_out;
+  std::vector<double> st(stamps, stamps + n);
+  HIP_TRY(d_st.upload(st, s));
+  HIP_TRY(d_out.reserve(size_t(36) * n));
+  const int grid = (n + kBlock / 64 - 1) / (kBlock / 64);
+  HS_ORDER_SWITCH(k, k_cov_sample<K><<<grid, kBlock, 0, s>>>(p->T, p->d_cov_band.p, n, d_st.p, d_out.p));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(cov, d_out.p, size_t(36) * n * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return HS_OK;
+}
+
 int hs_set_weights(hs_problem* p, int type, const double* weights) {
   if (!p) return HS_ERR_INVALID;
   if (type < HS_PIXEL || type > HS_INERTIAL) HS_FAIL(HS_ERR_INVALID, "unknown factor type");
@@ -748,6 +876,7 @@ int hs_solve(hs_problem* p, int max_iterations, hs_summary* summary, hs_iteratio
   if (p->has_weights()) HS_FAIL(HS_ERR_INVALID, kWeightsMessage);
   if (max_iterations < 0 || max_iterations > kMaxIterations) HS_FAIL(HS_ERR_INVALID, "max_iterations out of range");
   p->results_cached = false;
+  p->cov_valid = false;
   int rc = prepare(p);
   if (rc) return rc;
   const bool spec = speculative_solve(p);
@@ -898,6 +1027,7 @@ int hs_restore(hs_problem* p) {
   if (!p) return HS_ERR_INVALID;
   if (!p->has_snapshot || p->dirty) HS_FAIL(HS_ERR_STATE, "hs_restore without a valid hs_snapshot");
   p->results_cached = false;
+  p->cov_valid = false;
   HIP_TRY(hipMemcpyAsync(p->d_cp.p, p->d_cp_snap.p, p->cp.size() * 8, hipMemcpyDeviceToDevice, p->stream));
   if (p->n_lm) HIP_TRY(hipMemcpyAsync(p->d_lm.p, p->d_lm_snap.p, p->lm.size() * 8, hipMemcpyDeviceToDevice, p->stream));
   if (p->has_imu) {

@@ -220,7 +220,7 @@ struct hs_problem {
   // every solve; the delta interface — hs_append_* / hs_retire_* / hs_stage — keeps the rest resident between solves).
   enum : unsigned { kVis = 1, kPri = 2, kIne = 4, kTail = 8, kStructure = 15, vCp = 16, vCam = 32, vSensor = 64, vLm = 128, vImu = 256, vGravity = 512, vBias = 1024, kValues = 2032, kAll = 2047 };
   unsigned changed = kAll;
-  void touch(unsigned what) { changed |= what, dirty = true; }
+  void touch(unsigned what) { changed |= what, dirty = true, cov_valid = false; }
   bool device_ahead = false;  // hs_solve moved the point on the device and the host copies have not been refreshed since (pull_state)
 
   // host tables (caller's table order)
@@ -317,6 +317,12 @@ struct hs_problem {
   DBuf<double> d_cp_snap, d_lm_snap;
   bool has_snapshot = false;
   DevState* h_state = nullptr;  // pinned
+  // marginal covariances (hs_compute_covariance, kernels_covariance.hpp): allocated on first use; cov_valid until the state or a table changes
+  bool cov_valid = false;
+  int cov_np = 0, cov_ncb = 0, cov_nb = 0, cov_nlm = 0;
+  DBuf<double> d_cov_U, d_cov_sig, d_cov_Z, d_cov_X, d_cov_C, d_cov_Li, d_cov_band, d_cov_pb, d_cov_bb, d_cov_lm;
+  DBuf<uint8_t> d_cov_const;
+  DBuf<int> d_cov_status, d_cov_lm_status;
   std::vector<hipEvent_t> events;
   hipStream_t side = nullptr;           // second stream: the segment partials run next to the landmark pass (independent inputs)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_irec = nullptr;

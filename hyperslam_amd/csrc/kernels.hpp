@@ -34,3 +34,4 @@
 #include "kernels_update.hpp"
 #include "kernels_aux.hpp"
 #include "kernels_klt.hpp"
+#include "kernels_covariance.hpp"

@@ -317,6 +317,27 @@ class Problem:
         self._check(self.lib.reduced_system(self.h, float(radius), _d(S), _d(g)), "reduced_system")
         return S, g
 
+    def compute_covariance(self):
+        """Marginal covariances of the current state on the device (hs_compute_covariance; ceres::Covariance::Compute, DESIGN §12)."""
+        self._check(self.lib.compute_covariance(self.h), "compute_covariance")
+
+    def covariance(self):
+        """What compute_covariance() computed, in Ceres-local coordinates: control_points (n_cp, 6, 6), control_point_band (n_cp, bw, 6, 6) —
+        entry [i, j] is the block of control points (i, i + j) —, landmarks (n_lm, 3, 3) in table order, border (nb, nb) (bias splines, gravity)."""
+        n_cp, bw = self.window.n_cp, self.lib.band_blocks(self.h)
+        n_lm, nb = self.num_landmarks(), self.dim_pose() - 6 * n_cp
+        cpb, band = np.zeros((n_cp, 6, 6)), np.zeros((n_cp, bw, 6, 6))
+        lm, border = np.zeros((n_lm, 3, 3)), np.zeros((nb, nb))
+        self._check(self.lib.get_covariance(self.h, _d(cpb), _d(band), _d(lm), _d(border)), "get_covariance")
+        return dict(control_points=cpb, control_point_band=band, landmarks=lm, border=border)
+
+    def sample_covariance(self, stamps):
+        """Covariance (n, 6, 6) of the pose at each stamp, in the residual coordinates of the pose prior [rotation ; position]."""
+        st = _arr(stamps, _f64)
+        out = np.zeros((len(st), 6, 6))
+        self._check(self.lib.sample_covariance(self.h, len(st), _d(st), _d(out)), "sample_covariance")
+        return out
+
     def solve(self, max_iterations=5):
         """CeresOptimizer::optimize (optimizer.cpp:276-280; max_num_iterations = 5, optimizer.cpp:40)."""
         s = Summary()

@@ -218,6 +218,26 @@ int hs_cost(hs_problem* p, double* cost);
  * S (dim x dim, row-major, symmetric) and g (dim). What one LM iteration factors; parity target for the Schur build. */
 int hs_reduced_system(hs_problem* p, double radius, double* S, double* g);
 
+/* ---- marginal covariances (the counterpart of ceres::Covariance) ---------------------------------------- */
+/* The covariance is the inverse of the undamped Gauss-Newton matrix J'J at the values the device holds (what hs_get_* return), built as the
+ * solver builds it: robustified Jacobians (Ceres' loss corrector), landmarks eliminated by Schur complement, zero LM damping. Coordinates are
+ * Ceres-local, the columns of hs_linearize: control points [d_rot(3) d_trans(3)], landmarks Euclidean (3), bias control points R3 each,
+ * gravity the 2-dim SphereManifold basis; the border unknowns in the column order of hs_reduced_system (bias_g points, bias_a points, gravity).
+ * Constant control points / landmarks / bias splines / gravity have zero covariance (as in Ceres); sensor blocks are constant, as in the solver.
+ * A free coordinate without information (a structurally zero column, a non-positive pivot, or a pivot below 1e-12 of its Jacobi-scaled diagonal;
+ * per landmark: of its scaled 3x3 block) gives HS_ERR_NUMERIC with a message naming the control point, border unknown or landmark.
+ * Fixing the gauge is the caller's business: an almost singular gauge direction is not guaranteed to be caught.
+ * hs_compute_covariance computes everything on the device; any later change of values or tables, hs_solve and hs_restore make it stale and the
+ * getters then return HS_ERR_STATE. HS_ERR_INVALID while a weight matrix is set; HS_ERR_STATE for sharded handles (world > 1). */
+int hs_compute_covariance(hs_problem* p);
+/* cp_blocks n_cp x 6 x 6 (marginals); cp_band n_cp x bw x 6 x 6, entry (i, j) = block (i, i + j) (zero past the last control point,
+ * bw = hs_band_blocks); landmarks n_lm x 3 x 3 (table order; NaN for a landmark without residual rows: it is not in the problem);
+ * border nb x nb, nb = hs_dim_pose - 6 n_cp. Each pointer is nullable. */
+int hs_get_covariance(hs_problem* p, double* cp_blocks, double* cp_band, double* landmarks, double* border);
+/* Covariance of the pose at n stamps (n x 6 x 6, the residual coordinates of HS_PRIOR: [Log(R_m' R) ; p - p_m] with the measurement at the
+ * pose itself): J(t) Sigma J(t)' over the k control points the pose depends on. HS_ERR_INVALID for a stamp outside the valid range. */
+int hs_sample_covariance(hs_problem* p, int n, const double* stamps, double* cov);
+
 /* ---- solve ------------------------------------------------------------------------------------------------------ */
 /* Replaces CeresOptimizer::optimize (optimizer.cpp:276-280) with the options of optimizer.cpp:38-54 (trust-region LM,
  * Jacobi scaling, monotonic steps). iterations (nullable) receives max_iterations + 1 records (record 0 = initial point). */
