@@ -142,6 +142,9 @@ _PRODUCT_ONLY = {
     "rccl_shutdown": (C.c_int, [C.c_void_p]),
     "exchange_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     # marginal covariances (the oracle has no counterpart)
+    # free camera blocks (the oracle keeps every sensor block constant)
+    "set_camera_constancy": (C.c_int, [C.c_void_p, C.c_int, c_uint8_p]),
+    "get_cameras": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
     "compute_covariance": (C.c_int, [C.c_void_p]),
     "get_covariance": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "sample_covariance": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),

@@ -145,6 +145,8 @@ int hs_set_spline(hs_problem* p, int order, double t0, double dt, int n_cp, cons
   return HS_OK;
 }
 
+static const char* kCameraShardMessage = "free camera blocks (hs_set_camera_constancy) are not supported on sharded handles (world > 1)";
+
 int hs_set_cameras(hs_problem* p, int n, const double* T_bs, const double* intr, const double* dist) {
   if (!p) return HS_ERR_INVALID;
   if (n < 0 || n > 0xffff || (n && (!T_bs || !intr || !dist))) HS_FAIL(HS_ERR_INVALID, "bad camera table");
@@ -157,7 +159,36 @@ int hs_set_cameras(hs_problem* p, int n, const double* T_bs, const double* intr,
     std::memcpy(c, T_bs + 7 * i, 56), std::memcpy(c + 7, intr + 4 * i, 32), std::memcpy(c + 11, dist + 4 * i, 32);
   }
   if (same_count && before == p->cam) return HS_OK;
+  if (!same_count) p->cam_const.clear();  // (constancy flags are per camera: a table of another size starts from the default)
   p->touch(same_count ? unsigned(hs_problem::vCam) : unsigned(hs_problem::vCam | hs_problem::kVis));  // (the visual section checks the camera indices)
+  return HS_OK;
+}
+
+/// Manifold<Sensor>::setTransformationConstant, Manifold<Camera>::setIntrinsicsConstant / setDistortionConstant (sensor.cpp:26-29, camera.cpp:29-48).
+int hs_set_camera_constancy(hs_problem* p, int n, const uint8_t* constant) {
+  if (!p) return HS_ERR_INVALID;
+  std::vector<uint8_t> flags;
+  if (constant) {
+    if (n != p->n_cam) HS_FAIL(HS_ERR_INVALID, "hs_set_camera_constancy: n must equal the camera count of hs_set_cameras");
+    flags.resize(size_t(3) * n);
+    bool any_free = false;
+    for (size_t i = 0; i < flags.size(); ++i) flags[i] = constant[i] ? 1 : 0, any_free |= !flags[i];
+    if (!any_free) flags.clear();  // (every block constant: the default, and the same tables)
+  }
+  if (flags == p->cam_const) return HS_OK;
+  p->cam_const.swap(flags);
+  p->touch(hs_problem::kTail);  // (border layout and sizes)
+  return HS_OK;
+}
+
+int hs_get_cameras(hs_problem* p, double* T_bs, double* intr, double* dist) {
+  if (!p) return HS_ERR_INVALID;
+  for (int i = 0; i < p->n_cam; ++i) {
+    const double* c = &p->cam[size_t(kCamStride) * i];
+    if (T_bs) std::memcpy(T_bs + 7 * i, c, 56);
+    if (intr) std::memcpy(intr + 4 * i, c + 7, 32);
+    if (dist) std::memcpy(dist + 4 * i, c + 11, 32);
+  }
   return HS_OK;
 }
 
@@ -395,7 +426,7 @@ int hs_num_residuals(hs_problem* p, int type) {
   }
   return -1;
 }
-int hs_dim_pose(hs_problem* p) { return p ? 6 * p->n_cp + (p->has_imu ? 6 * p->n_bias + 2 : 0) : -1; }
+int hs_dim_pose(hs_problem* p) { return p ? 6 * p->n_cp + (p->has_imu ? 6 * p->n_bias + 2 : 0) + camera_columns(p, nullptr) : -1; }
 
 int hs_residual_layout(hs_problem* p, int type, int idx, int32_t* num_blocks, int32_t* indices, int32_t* sizes, int32_t* offsets, int32_t* block_ids,
                        int32_t* num_parameters, int32_t* num_residuals) {
@@ -681,6 +712,7 @@ int hs_cost(hs_problem* p, double* cost) {
 int hs_reduced_system(hs_problem* p, double radius, double* S, double* g) {
   if (!p || !S || !g) return HS_ERR_INVALID;
   if (p->has_weights()) HS_FAIL(HS_ERR_INVALID, kWeightsMessage);
+  if (p->world > 1 && camera_columns(p, nullptr)) HS_FAIL(HS_ERR_STATE, kCameraShardMessage);
   int rc = prepare(p);
   if (rc) return rc;
   rc = reset_state(p, 1, radius);
@@ -731,6 +763,7 @@ int hs_compute_covariance(hs_problem* p) {
   if (!p) return HS_ERR_INVALID;
   if (p->has_weights()) HS_FAIL(HS_ERR_INVALID, kWeightsMessage);
   if (p->world > 1) HS_FAIL(HS_ERR_STATE, "hs_compute_covariance: sharded handles (world > 1) are not supported");
+  if (camera_columns(p, nullptr)) HS_FAIL(HS_ERR_STATE, "hs_compute_covariance: free camera blocks (hs_set_camera_constancy) are not supported");
   p->cov_valid = false;
   int rc = prepare(p);
   if (rc) return rc;
@@ -875,6 +908,11 @@ int hs_solve(hs_problem* p, int max_iterations, hs_summary* summary, hs_iteratio
   if (!p || !summary) return HS_ERR_INVALID;
   if (p->has_weights()) HS_FAIL(HS_ERR_INVALID, kWeightsMessage);
   if (max_iterations < 0 || max_iterations > kMaxIterations) HS_FAIL(HS_ERR_INVALID, "max_iterations out of range");
+  if (camera_columns(p, nullptr)) {
+    if (p->world > 1) HS_FAIL(HS_ERR_STATE, kCameraShardMessage);
+    HS_FAIL(HS_ERR_STATE, "hs_solve: free camera blocks (hs_set_camera_constancy) are not supported by the solver in this version; "
+                          "hs_reduced_system builds their system (DESIGN.md section 13)");
+  }
   p->results_cached = false;
   p->cov_valid = false;
   int rc = prepare(p);

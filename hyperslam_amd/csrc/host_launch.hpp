@@ -46,7 +46,7 @@ template <int K>
 int launch_linearize(hs_problem* p, bool inertial_on_side = false, bool visual_cost_only = false) {
   const Tables& T = p->T;
   hipStream_t s = p->stream;
-  p->side_imu = inertial_on_side && T.n_ine > 0 && T.nb > 0 && !(T.debug_flags & 1048576);  // A/B switch 1048576: one stream
+  p->side_imu = inertial_on_side && T.n_ine > 0 && T.nb > 0 && !T.nc && !(T.debug_flags & 1048576);  // A/B switch 1048576: one stream
   if (p->side_imu) {
     const int rc = ensure_side_stream(p);
     if (rc) return rc;
@@ -256,9 +256,18 @@ int launch_build(hs_problem* p, hipEvent_t after_build = nullptr, bool scaling_f
     HIP_TRY(hipGetLastError());
     return HS_OK;
   }
-  if (T.nb && !side_imu) {
+  if (T.nb > T.nc && !side_imu) {  // (bias / gravity columns: with an IMU only — free camera columns alone are not gathered here)
     k_border_pb<K><<<dim3(T.sp.n_cp + border_zero_wgs(T), p->n_split), kPbThreads, 0, s>>>(T);
     k_border_bb<K><<<T.n_bias, kBlock, 0, s>>>(T);
+  }
+  if (T.nc) {  // free camera coordinates (kernels_calib.hpp): behind the landmark factors and the IMU gathers, on the main stream
+    const int n_row_chunks = (T.n_vis + kCalibRowChunk - 1) / kCalibRowChunk, n_parts = n_row_chunks + (T.n_lm + kCalibLmChunk - 1) / kCalibLmChunk;
+    const int E = T.nc * T.nc + 2 * T.nc;
+    if (T.n_vis) k_calib_rows<K><<<(T.n_vis + kBlock - 1) / kBlock, kBlock, 0, s>>>(T);
+    if (T.n_lm) k_calib_landmark<<<(T.n_lm + kBlock / 64 - 1) / (kBlock / 64), kBlock, 0, s>>>(T);
+    k_calib_pc<K><<<T.sp.n_cp, kBlock, 0, s>>>(T, p->n_split);
+    if (n_parts) k_calib_cc<<<n_parts, kBlock, 0, s>>>(T, n_row_chunks);
+    k_calib_finish<<<(E + kBlock - 1) / kBlock, kBlock, 0, s>>>(T, n_parts);
   }
   if (side_imu && !gather_flag) HIP_TRY(hipStreamWaitEvent(s, p->ev_join, 0));  // border gathers done
   // Nothing to exchange (single shard): packing + bookkeeping are an extra workgroup of k_finalize_reduced, the border blocks further

@@ -231,6 +231,7 @@ struct hs_problem {
   int rot_const = 0, trans_const = 0;
   int n_cam = 0;
   std::vector<double> cam;  // n x 16
+  std::vector<uint8_t> cam_const;  // hs_set_camera_constancy: n x 3 [T_bs, intrinsics, distortion]; empty: every block constant (camera.hpp:18)
   int n_sensor = 0;
   std::vector<double> sensor;  // n x 8
   int n_lm = 0;
@@ -323,6 +324,11 @@ struct hs_problem {
   DBuf<double> d_cov_U, d_cov_sig, d_cov_Z, d_cov_X, d_cov_C, d_cov_Li, d_cov_band, d_cov_pb, d_cov_bb, d_cov_lm;
   DBuf<uint8_t> d_cov_const;
   DBuf<int> d_cov_status, d_cov_lm_status;
+  // free camera blocks (kernels_calib.hpp): allocated by the first prepare() that has one
+  int nc = 0;                    // free camera coordinates in the system (camera_columns)
+  std::vector<int> calib_map;    // nc: camera << 8 | column inside the camera's 14
+  DBuf<int> d_calib_map;
+  DBuf<double> d_calib_rec, d_calib_Yc, d_calib_part;
   std::vector<hipEvent_t> events;
   hipStream_t side = nullptr;           // second stream: the segment partials run next to the landmark pass (independent inputs)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_irec = nullptr;
@@ -375,6 +381,27 @@ static const char* kWeightsMessage =
 namespace {
 
 int mfma_window_tiles(int bw);
+
+/// Border columns of the free camera coordinates, in the order of hs_reduced_system: per camera in table order the free blocks
+/// [T_bs 6 | intrinsics 4 | distortion 4]. A camera no visual residual references is not in the problem (Ceres' reduced program drops
+/// parameter blocks without residual blocks); a referenced camera keeps every free coordinate, all-zero columns included. `map`: nullable.
+static int camera_columns(const hs_problem* p, std::vector<int>* map) {
+  if (map) map->clear();
+  if (p->cam_const.empty()) return 0;
+  std::vector<uint8_t> used(p->n_cam, 0);
+  for (int32_t c : p->px_cam)
+    if (c >= 0 && c < p->n_cam) used[c] = 1;
+  for (int32_t c : p->br_cam)
+    if (c >= 0 && c < p->n_cam) used[c] = 1;
+  static const int first[3] = {0, 6, 10}, size[3] = {6, 4, 4};
+  int n = 0;
+  for (int c = 0; c < p->n_cam; ++c)
+    for (int b = 0; b < 3; ++b)
+      if (used[c] && !p->cam_const[3 * c + b])
+        for (int j = 0; j < size[b]; ++j, ++n)
+          if (map) map->push_back(c << 8 | (first[b] + j));
+  return n;
+}
 
 /// Value tables whose content changed (hs_problem::changed): control points + constancy mask, cameras, sensors, landmarks (device order), IMU
 /// parameters, gravity, bias points. Sizes, indices and sort orders are those of the last structural prepare().
@@ -668,7 +695,7 @@ int prepare(hs_problem* p) {
   HIP_TRY(p->d_g_s.reserve(np));
   HIP_TRY(p->d_g_full.reserve(np));
   HIP_TRY(p->d_D2p.reserve(np));
-  HIP_TRY(p->d_gabs.reserve(np + (p->has_imu ? 6 * p->n_bias + 2 : 0) + 1));
+  HIP_TRY(p->d_gabs.reserve(np + (p->has_imu ? 6 * p->n_bias + 2 : 0) + camera_columns(p, nullptr) + 1));
   HIP_TRY(p->d_step_p.reserve(np));
   HIP_TRY(p->d_delta_p.reserve(np));
   int vis_block = 0;
@@ -688,13 +715,28 @@ int prepare(hs_problem* p) {
   HIP_TRY(p->d_cand_part.reserve(p->nb_vis + p->nb_pri + p->nb_ine + 1));
   const int nb_norm = p->nb_cp;
   HIP_TRY(p->d_norm_part.reserve(2 * size_t(nb_norm)));
-  const int nbd = p->has_imu ? 6 * p->n_bias + 2 : 0;
-  if (nbd && size_t(np) * 8 * 8 > 150 * 1024) HS_FAIL(HS_ERR_INVALID, "window too long for the LDS-resident border forward sweep");
+  p->nc = camera_columns(p, &p->calib_map);
+  if (p->nc > kCalibMaxCols)
+    HS_FAIL(HS_ERR_INVALID, "too many free camera coordinates: at most " + std::to_string(kCalibMaxCols) + " per window (kCalibMaxCols), " +
+                                std::to_string(p->nc) + " requested (hs_set_camera_constancy)");
+  const int nbi = p->has_imu ? 6 * p->n_bias + 2 : 0;  // bias splines + gravity
+  const int nbd = nbi + p->nc;                          // border unknowns: those, then the free camera coordinates
+  // (the two limits below belong to the solver's bordered factorisation — k_border_forward, k_border_solve —, which a handle with free camera
+  //  coordinates does not reach in this version (hs_solve refuses it): they count the bias / gravity columns only)
+  if (nbi && size_t(np) * 8 * 8 > 150 * 1024) HS_FAIL(HS_ERR_INVALID, "window too long for the LDS-resident border forward sweep");
   // (k_border_solve: the border Schur complement, augmented, in LDS — (nb + 1)^2 + nb doubles within the 150 KB the kernel may ask for: nb <= 137,
   //  i.e. 22 bias control points; the launch used to fail inside hs_solve with "invalid argument")
-  if (nbd + 1 > 128 && (size_t(nbd + 1) * (nbd + 1) + nbd) * sizeof(double) > size_t(150) * 1024)
+  if (nbi + 1 > 128 && (size_t(nbi + 1) * (nbi + 1) + nbi) * sizeof(double) > size_t(150) * 1024)
     HS_FAIL(HS_ERR_INVALID, "too many border unknowns (bias control points) for the LDS-resident dense solve of the border system: at most 22 bias control points per window");
-  const int x_count1 = np * (ncb + 3) + np * nbd + nbd * nbd + nbd + 1 + p->world;
+  const int x_count0 = np * (ncb + 3) + np * nbd + nbd * nbd + nbd + 1 + p->world;
+  const int x_count1 = x_count0 + p->nc;  // (+ diag(J'J) of the camera columns)
+  if (p->nc) {
+    HIP_TRY(p->d_calib_map.upload(p->calib_map, s));
+    HIP_TRY(p->d_calib_rec.reserve(size_t(std::max(n_vis, 1)) * (40 + 12 * k)));
+    HIP_TRY(p->d_calib_Yc.reserve(size_t(std::max(p->n_lm, 1)) * 3 * p->nc));
+    const int n_parts = (n_vis + kCalibRowChunk - 1) / kCalibRowChunk + (p->n_lm + kCalibLmChunk - 1) / kCalibLmChunk;
+    HIP_TRY(p->d_calib_part.reserve(size_t(std::max(n_parts, 1)) * (p->nc * p->nc + 2 * p->nc)));
+  }
   HIP_TRY(p->d_ybuf.reserve(np));
   HIP_TRY(p->d_scale_b.reserve(nbd + 1));
   HIP_TRY(p->d_Spb.reserve(size_t(np) * nbd + 1));
@@ -821,7 +863,8 @@ int prepare(hs_problem* p) {
   T.bias_g = p->d_bias_g.p, T.bias_a = p->d_bias_a.p, T.bias_g_cand = p->d_bias_g_cand.p, T.bias_a_cand = p->d_bias_a_cand.p;
   T.gravity = p->d_gravity.p, T.gravity_cand = p->d_gravity_cand.p, T.bias_const = p->bias_const, T.gravity_const = p->gravity_const;
   T.inertial_literal = p->inertial_mode == HS_INERTIAL_AS_REFERENCE;
-  T.nb = p->has_imu ? 6 * p->n_bias + 2 : 0;
+  T.nb = (p->has_imu ? 6 * p->n_bias + 2 : 0) + p->nc;
+  T.nc = p->nc, T.calib_map = p->d_calib_map.p, T.calib_rec = p->d_calib_rec.p, T.calib_Yc = p->d_calib_Yc.p, T.calib_part = p->d_calib_part.p;
   T.n_seg = n_seg, T.bw = vs.bw, T.np = np;
   T.scale_p = p->d_scale_p.p, T.Sb = p->d_Sb.p, T.Ub = p->d_Ub.p, T.Ubk = p->d_Ubk.p, T.g_s = p->d_g_s.p, T.g_full = p->d_g_full.p, T.D2p = p->d_D2p.p, T.gabs = p->d_gabs.p;
   T.step_p = p->d_step_p.p, T.delta_p = p->d_delta_p.p;
@@ -845,7 +888,7 @@ int prepare(hs_problem* p) {
   }
   T.scale_b = p->d_scale_b.p, T.Spb = p->d_Spb.p, T.Sbb = p->d_Sbb.p, T.gb_s = p->d_gb_s.p, T.D2b = p->d_D2b.p;
   T.Zb = p->d_Zb.p, T.Cb = p->d_Cb.p, T.hb = p->d_hb.p, T.xb = p->d_xb.p, T.delta_b = p->d_delta_b.p, T.i_bias_ptr = p->d_i_bias_ptr.p, T.bfwd_start = p->d_bfwd_start.p;
-  T.x_count1 = x_count1, T.xo_dec = x_count1;
+  T.x_count1 = x_count1, T.xo_dec = x_count1, T.xo_cdj = x_count0;
   T.fused = p->fused ? 1 : 0, T.n_chunk = p->fused ? p->n_group_wg : 0, T.ch_ptr = p->d_ch_ptr.p, T.ch_desc = p->d_ch_desc.p;
   T.build_stream_lg = p->fused ? build_streams_packed(vs.bw, k) : 0;
   T.ch_gmax = p->d_ch_gmax.p;

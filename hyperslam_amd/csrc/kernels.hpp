@@ -35,3 +35,4 @@
 #include "kernels_aux.hpp"
 #include "kernels_klt.hpp"
 #include "kernels_covariance.hpp"
+#include "kernels_calib.hpp"

@@ -283,7 +283,11 @@ HSD void finalize_border_body(const Tables& T, const int wg, const int n_wg, con
   if (T.gather_epoch) gather_wait(T);
   const int nb = T.nb, np = T.np;
   const double* X = T.xbuf;
-  auto sb_of = [&](int b) { return fresh ? 1.0 / (1.0 + sqrt(X[T.xo_bb + size_t(b) * nb + b])) : T.scale_b[b]; };
+  // diag(J'J) of border column b: the diagonal of H_bb for the bias / gravity columns; the camera columns (the last T.nc) keep theirs apart,
+  // their H_bb block is a Schur complement (kernels_calib.hpp)
+  const int nbi = nb - T.nc;
+  auto dj_of = [&](int b) { return b < nbi ? X[T.xo_bb + size_t(b) * nb + b] : X[T.xo_cdj + (b - nbi)]; };
+  auto sb_of = [&](int b) { return fresh ? 1.0 / (1.0 + sqrt(dj_of(b))) : T.scale_b[b]; };
   auto sp_of = [&](int rho) { return fresh ? 1.0 / (1.0 + sqrt(X[T.xo_dj + rho])) : T.scale_p[rho]; };
   const int total = (np + nb) * nb;
   for (int e = wg * blockDim.x + threadIdx.x; e < total; e += n_wg * blockDim.x) {
@@ -314,7 +318,7 @@ HSD void finalize_border_body(const Tables& T, const int wg, const int n_wg, con
       const double sr = sb_of(b), sc = sb_of(c);
       double out = sr * sc * X[T.xo_bb + size_t(b) * nb + c];
       if (b == c) {
-        const double d = X[T.xo_bb + size_t(b) * nb + b];
+        const double d = dj_of(b);
         if (d > 0.0) {
           const double d2 = fmin(fmax(sr * sr * d, 1e-6), 1e32) / radius;
           out += d2;

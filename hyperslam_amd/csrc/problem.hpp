@@ -169,7 +169,12 @@ struct Tables {
   double* gravity_cand;
   int bias_const, gravity_const;
   int inertial_literal;  // Jacobian of the inertial factor as written upstream (inertial.cpp:131-198) | 0: derivative of the prediction
-  int nb;                  // border unknowns: 6 n_bias + 2 (0 without an IMU)
+  int nb;                  // border unknowns: 6 n_bias + 2 (0 without an IMU), then the nc free camera coordinates
+  int nc;                  // free camera coordinates in the system (hs_set_camera_constancy; the last nc border columns, kernels_calib.hpp)
+  const int* calib_map;    // nc: camera << 8 | column inside the camera's [T_bs 6 | intrinsics 4 | distortion 4]
+  double* calib_rec;       // n_vis x calib_record<K>() (segment-major slots)
+  double* calib_Yc;        // n_lm x 3 x nc   Y_c = L^-1 S_l H_lc
+  double* calib_part;      // partials of k_calib_cc
   // reduced system
   int bw;                  // band width in blocks
   int np;                  // 6 * n_cp
@@ -229,6 +234,7 @@ struct Tables {
   double* grpQ;   // per k_group_gram workgroup: [upper 6x6 tiles of -sum Yh Yh' | -sum Yh yh (6 bw)]
   double* xpart;  // per-split partial copies of the H_pb part of the exchange buffer (stride x_count1); scratch for timestamps
   int xo_g, xo_gs, xo_dj, xo_pb, xo_bb, xo_gb, xo_cost, xo_gmax, xo_dec, x_count1;
+  int xo_cdj;     // nc > 0: diag(J'J) of the camera columns (the Jacobi scale; the border-border block holds their Schur complement)
   // fused build of the visual factors (kernels_build.hpp): chunk w = device landmarks [ch_ptr[w], ch_ptr[w + 1]) of one landmark group;
   // gw_ptr / gw_cf then list the chunks of a group and grpQ holds one partial [tiles | -Yh yh | J_p'r | diag J_p'J_p] per chunk
   int fused, n_chunk;

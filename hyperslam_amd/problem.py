@@ -49,6 +49,7 @@ class Window:
     cam_T_bs: np.ndarray = field(default_factory=lambda: np.zeros((0, 7)))
     cam_intrinsics: np.ndarray = field(default_factory=lambda: np.zeros((0, 4)))
     cam_distortion: np.ndarray = field(default_factory=lambda: np.zeros((0, 4)))
+    cam_constant: np.ndarray | None = None  # n_cam x 3 [T_bs, intrinsics, distortion], non-zero = constant; None: every block constant
     sensor_T_bs: np.ndarray = field(default_factory=lambda: np.zeros((0, 7)))
     landmarks: np.ndarray = field(default_factory=lambda: np.zeros((0, 3)))
     landmark_constant: np.ndarray | None = None
@@ -136,6 +137,10 @@ class Problem:
                                  int(w.rotation_constant), int(w.translation_constant)), "set_spline")
         T, I, D = _arr(w.cam_T_bs, _f64, (-1, 7)), _arr(w.cam_intrinsics, _f64, (-1, 4)), _arr(w.cam_distortion, _f64, (-1, 4))
         self._check(L.set_cameras(h, T.shape[0], _d(T), _d(I), _d(D)), "set_cameras")
+        if hasattr(L, "set_camera_constancy"):  # (None: every block constant, like cp_constant / landmark_constant)
+            self.set_camera_constancy(w.cam_constant)
+        elif w.cam_constant is not None and np.any(np.asarray(w.cam_constant) == 0):
+            raise HsError(f"{L.prefix}set_camera_constancy: not provided by this library (sensor blocks are constant there)")
         S = _arr(w.sensor_T_bs, _f64, (-1, 7))
         self._check(L.set_sensors(h, S.shape[0], _d(S)), "set_sensors")
         lm = _arr(w.landmarks, _f64, (-1, 3))
@@ -349,6 +354,23 @@ class Problem:
         summary = {f[0]: getattr(s, f[0]) for f in Summary._fields_}
         summary["iterations"] = iterations
         return summary
+
+    def set_camera_constancy(self, constant):
+        """Which camera blocks stay constant: (n_cam, 3) flags [T_bs, intrinsics, distortion], non-zero = constant; None = all (the default)."""
+        if not hasattr(self.lib, "set_camera_constancy"):
+            raise HsError(f"{self.lib.prefix}set_camera_constancy: not provided by this library (sensor blocks are constant there)")
+        if constant is None:
+            self._check(self.lib.set_camera_constancy(self.h, 0, None), "set_camera_constancy")
+            return
+        c = _arr(constant, np.uint8, (-1, 3))
+        self._check(self.lib.set_camera_constancy(self.h, c.shape[0], _u8(c)), "set_camera_constancy")
+
+    def cameras(self):
+        """Current camera values (T_bs (n, 7), intrinsics (n, 4), distortion (n, 4)) in the layout of the window's tables."""
+        n = len(_arr(self.window.cam_T_bs, _f64, (-1, 7)))
+        T, I, D = np.zeros((n, 7)), np.zeros((n, 4)), np.zeros((n, 4))
+        self._check(self.lib.get_cameras(self.h, _d(T), _d(I), _d(D)), "get_cameras")
+        return T, I, D
 
     def snapshot(self):
         self._check(self.lib.snapshot(self.h), "snapshot")

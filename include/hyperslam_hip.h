@@ -128,6 +128,18 @@ int hs_set_spline(hs_problem* p, int order, double t0, double dt, int n_cp, cons
 /* Replaces setSensorManifold for cameras (optimizer.cpp:143-155; constant blocks, camera.hpp:18).
  * T_bs n x 7, intrinsics n x 4 [cx cy fx fy] (settings.yaml:38-40), distortion n x 4 radtan [k1 k2 p1 p2] (:42-45). */
 int hs_set_cameras(hs_problem* p, int n, const double* T_bs, const double* intrinsics, const double* distortion);
+/* Camera blocks the solver may estimate (Manifold<Sensor>::setTransformationConstant, Manifold<Camera>::setIntrinsicsConstant /
+ * setDistortionConstant). constant: n x 3 flags [transformation, intrinsics, distortion] per camera, n = the camera count of
+ * hs_set_cameras; non-zero keeps the block constant. NULL restores the default: every block constant (camera.hpp:18). A camera table of
+ * another size resets the flags. Free coordinates are border unknowns behind bias_g, bias_a and gravity (hs_reduced_system), per camera in
+ * table order the free blocks [T_bs 6 | intrinsics 4 | distortion 4], Ceres-local: T_bs on HS_MANIFOLD_SE3 [d_rot(3) d_trans(3)],
+ * intrinsics [cx cy fx fy] and radtan [k1 k2 p1 p2] Euclidean. Pixel residuals touch all three blocks of their camera, bearing residuals
+ * T_bs only (their intrinsics / distortion columns are zero). A camera no visual residual references is left out. At most 64 free camera
+ * coordinates per window (HS_ERR_INVALID from the call that prepares the tables). In this version hs_solve and hs_compute_covariance
+ * refuse a handle with free camera coordinates (HS_ERR_STATE), and so does hs_reduced_system on a sharded handle (world > 1). */
+int hs_set_camera_constancy(hs_problem* p, int n, const uint8_t* constant);
+/* Current camera values in the layout of hs_set_cameras (n x 7, n x 4, n x 4). Each pointer may be NULL. */
+int hs_get_cameras(hs_problem* p, double* T_bs, double* intrinsics, double* distortion);
 /* Plain sensors (extrinsics only) used by pose-prior factors (manifold.cpp:30-33). T_bs n x 7. */
 int hs_set_sensors(hs_problem* p, int n, const double* T_bs);
 /* Replaces addLandmark/updateLandmarks (optimizer.cpp:347-382). xyz n x 3; constant may be NULL. */
@@ -196,7 +208,7 @@ int hs_residual_layout(hs_problem* p, int type, int idx, int32_t* num_blocks, in
 
 /* ---- evaluation (parity / debugging surface) ------------------------------------------------------------------ */
 int hs_num_residuals(hs_problem* p, int type);
-int hs_dim_pose(hs_problem* p); /* 6*n_cp (+ 6*n_bias + 2 with an IMU): size of the reduced system */
+int hs_dim_pose(hs_problem* p); /* 6*n_cp (+ 6*n_bias + 2 with an IMU) (+ free camera coordinates): size of the reduced system */
 /* Batched replacement of ExteroceptiveCost::Evaluate + Ceres' local-Jacobian projection for every residual of `type`.
  * robustify != 0 additionally applies Ceres' loss corrector (sqrt(rho') scaling of r and J). */
 int hs_linearize(hs_problem* p, int type, int robustify, const hs_linearization* out);
@@ -215,7 +227,8 @@ int hs_set_weights(hs_problem* p, int type, const double* weights);
 /* Total cost 0.5*sum rho(|r|^2) at the current point. */
 int hs_cost(hs_problem* p, double* cost);
 /* Reduced (landmark-eliminated), Jacobi-scaled, LM-damped system of the first iteration at the current point:
- * S (dim x dim, row-major, symmetric) and g (dim). What one LM iteration factors; parity target for the Schur build. */
+ * S (dim x dim, row-major, symmetric) and g (dim). What one LM iteration factors; parity target for the Schur build.
+ * Columns: control points, then the border: bias_g points, bias_a points, gravity, free camera coordinates (hs_set_camera_constancy). */
 int hs_reduced_system(hs_problem* p, double radius, double* S, double* g);
 
 /* ---- marginal covariances (the counterpart of ceres::Covariance) ---------------------------------------- */
