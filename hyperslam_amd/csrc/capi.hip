@@ -181,6 +181,16 @@ int hs_set_camera_constancy(hs_problem* p, int n, const uint8_t* constant) {
   return HS_OK;
 }
 
+/// hs_solve estimates the free camera blocks of this handle (off by default: it refuses them).
+int hs_set_camera_estimation(hs_problem* p, int enabled) {
+  if (!p) return HS_ERR_INVALID;
+  const bool on = enabled != 0;
+  if (on == p->cam_estimation) return HS_OK;
+  p->cam_estimation = on;
+  if (camera_columns(p, nullptr)) p->touch(hs_problem::kTail);  // (the border limits of prepare() depend on it)
+  return HS_OK;
+}
+
 int hs_get_cameras(hs_problem* p, double* T_bs, double* intr, double* dist) {
   if (!p) return HS_ERR_INVALID;
   for (int i = 0; i < p->n_cam; ++i) {
@@ -910,8 +920,9 @@ int hs_solve(hs_problem* p, int max_iterations, hs_summary* summary, hs_iteratio
   if (max_iterations < 0 || max_iterations > kMaxIterations) HS_FAIL(HS_ERR_INVALID, "max_iterations out of range");
   if (camera_columns(p, nullptr)) {
     if (p->world > 1) HS_FAIL(HS_ERR_STATE, kCameraShardMessage);
-    HS_FAIL(HS_ERR_STATE, "hs_solve: free camera blocks (hs_set_camera_constancy) are not supported by the solver in this version; "
-                          "hs_reduced_system builds their system (DESIGN.md section 13)");
+    if (!p->cam_estimation)  // (estimating them is opt-in per handle: hs_set_camera_estimation)
+      HS_FAIL(HS_ERR_STATE, "hs_solve: free camera blocks (hs_set_camera_constancy) are not supported by the solver in this version; "
+                            "hs_reduced_system builds their system (DESIGN.md section 13)");
   }
   p->results_cached = false;
   p->cov_valid = false;
@@ -985,6 +996,9 @@ int hs_solve(hs_problem* p, int max_iterations, hs_summary* summary, hs_iteratio
     }
     if (p->has_imu) HIP_TRY(hipMemcpyAsync(h + n_cp8 + n_lm3 + 2 * n_b, p->d_gravity.p, 24, hipMemcpyDeviceToHost, s));  // also with an empty bias table
   }
+  // Estimated cameras: the host table follows the device right here (16 doubles per camera), so hs_get_cameras, the result cache, a later
+  // upload of the camera table and the evaluation calls that send it (hs_process_tracks, hs_sample_trajectory) all see the estimate.
+  if (p->T.nc && max_iterations > 0) HIP_TRY(hipMemcpyAsync(p->cam.data(), p->d_cam.p, p->cam.size() * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(&st, p->d_state.p, sizeof(st), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (max_iterations > 0) p->device_ahead = true;
@@ -1057,6 +1071,7 @@ int hs_snapshot(hs_problem* p) {
     HIP_TRY(hipMemcpyAsync(p->d_bias_a_snap.p, p->d_bias_a.p, p->bias_a.size() * 8, hipMemcpyDeviceToDevice, p->stream));
     HIP_TRY(hipMemcpyAsync(p->d_gravity_snap.p, p->d_gravity.p, 24, hipMemcpyDeviceToDevice, p->stream));
   }
+  p->cam_snap = p->cam;  // (the host table equals the device's: hs_solve keeps it so)
   p->has_snapshot = true;
   return HS_OK;
 }
@@ -1072,6 +1087,11 @@ int hs_restore(hs_problem* p) {
     HIP_TRY(hipMemcpyAsync(p->d_bias_g.p, p->d_bias_g_snap.p, p->bias_g.size() * 8, hipMemcpyDeviceToDevice, p->stream));
     HIP_TRY(hipMemcpyAsync(p->d_bias_a.p, p->d_bias_a_snap.p, p->bias_a.size() * 8, hipMemcpyDeviceToDevice, p->stream));
     HIP_TRY(hipMemcpyAsync(p->d_gravity.p, p->d_gravity_snap.p, 24, hipMemcpyDeviceToDevice, p->stream));
+  }
+  if (p->cam != p->cam_snap && p->cam.size() == p->cam_snap.size()) {  // cameras estimated since the snapshot
+    p->cam = p->cam_snap;
+    HIP_TRY(hipMemcpyAsync(p->d_cam.p, p->cam.data(), p->cam.size() * 8, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
   }
   return HS_OK;
 }

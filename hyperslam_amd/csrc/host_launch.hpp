@@ -125,6 +125,7 @@ static bool factor_two_ended_any(const hs_problem* p) {
   const int n_blk = T.np / 6;
   const bool la_ok = !(T.debug_flags & 4) && la_compute_waves(T.bw) > 0;
   const int nt = HS_AB(T.debug_flags, 131072) ? mfma_window_tiles(T.bw) : 0;
+  if (T.nc) return false;  // free camera coordinates: always one-ended (k_dense_solve_mx, or the band kernels + k_border_forward / _schur / _solve / _apply)
   return (la_ok || nt) && (T.nb == 0 || (!nt && !(T.debug_flags & 536870912) && (T.nb + kBorderCols - 1) / kBorderCols <= 512)) && n_blk >= 4 * T.bw && T.Sb2 &&
          !(T.debug_flags & 2048);  // (512: flag words of k_border_forward2's column groups)
 }
@@ -267,7 +268,7 @@ int launch_build(hs_problem* p, hipEvent_t after_build = nullptr, bool scaling_f
     if (T.n_lm) k_calib_landmark<<<(T.n_lm + kBlock / 64 - 1) / (kBlock / 64), kBlock, 0, s>>>(T);
     k_calib_pc<K><<<T.sp.n_cp, kBlock, 0, s>>>(T, p->n_split);
     if (n_parts) k_calib_cc<<<n_parts, kBlock, 0, s>>>(T, n_row_chunks);
-    k_calib_finish<<<(E + kBlock - 1) / kBlock, kBlock, 0, s>>>(T, n_parts);
+    k_calib_finish<<<(E + kBlock - 1) / kBlock, kBlock, 0, s>>>(T, n_parts, n_row_chunks);
   }
   if (side_imu && !gather_flag) HIP_TRY(hipStreamWaitEvent(s, p->ev_join, 0));  // border gathers done
   // Nothing to exchange (single shard): packing + bookkeeping are an extra workgroup of k_finalize_reduced, the border blocks further
@@ -541,7 +542,8 @@ int launch_factor(hs_problem* p) {
     const int fwd_threads = std::max(128, 64 * ((6 * (T.bw - 1) + 63) / 64));  // one lane per pending row
     // the first non-zero row of a border column follows from the inertial record table — of ALL shards: a shard of a distributed solve
     // only skips the rows of the constant control points (which every shard agrees on)
-    const int local_rows = (!p->allreduce && !p->rccl_comm && p->world == 1) ? 1 : 0;
+    // (a free camera column is dense over every control point with visual rows: no row of it is skipped either — its bfwd_start is zero)
+    const int local_rows = (!p->allreduce && !p->rccl_comm && p->world == 1 && !T.nc) ? 1 : 0;
     k_border_forward<<<(T.nb + kBorderCols - 1) / kBorderCols, fwd_threads, size_t(T.np) * kBorderLd * sizeof(double), s>>>(T, f0, local_rows);
     const int nt = (T.nb + kSchurTile - 1) / kSchurTile;
     k_border_schur<<<dim3(nt, nt), kBlock, 0, s>>>(T, f0, local_rows, n_blk);
@@ -617,33 +619,48 @@ int launch_update(hs_problem* p, bool linearize_candidate = false, bool deferred
   // Single shard, fused path (round 6): the candidate costs of the prior / inertial factors are further workgroups of k_update_visual's launch —
   // one launch where a stereo-inertial window had three on the chain of every iteration. A/B switch 134217728: the separate launches.
   const bool merged = p->fused && local_decision && !(T.debug_flags & 134217728);
+  // Free camera coordinates (hs_set_camera_estimation): k_calib_candidate retracts the candidate camera table from the border step in front of
+  // the update; the kernels that evaluate the candidate's visual cost get that table as T.cam (Tc). Its norms are one more pair behind the
+  // norm workgroups' (slot n_norm_part), which only the decision kernel counts (Td).
+  Tables calib_tables[2];  // (filled for a handle with free camera coordinates only)
+  if (T.nc) {
+    k_calib_candidate<<<1, kBlock, 0, s>>>(T, p->d_cam_cand.p, T.n_norm_part);
+    calib_tables[0] = calib_tables[1] = T;
+    calib_tables[0].cam = p->d_cam_cand.p, calib_tables[1].n_norm_part = T.n_norm_part + 1;
+  }
+  const Tables &Tc = T.nc ? calib_tables[0] : T, &Td = T.nc ? calib_tables[1] : T;
   if (p->fused) {  // candidate point, landmark back-substitution and the visual candidate cost per chunk, one launch
     const int nb_pri = merged && T.n_pri ? p->nb_pri : 0, nb_ine = merged && T.n_ine ? p->nb_ine : 0;
     const size_t lds = std::max(size_t(update_lds_doubles(T.bw, p->build_R, p->build_L)), size_t(8 * T.sp.n_cp + 8 * T.n_bias + 4)) * 8;
-    k_update_visual<K><<<p->nb_vis + T.n_norm_part + nb_pri + nb_ine, kBlock, lds, s>>>(T, p->build_R, p->build_L, p->nb_vis, nb_pri, nb_ine);
+    if (T.nc)
+      k_update_visual<K, true><<<p->nb_vis + T.n_norm_part + nb_pri + nb_ine, kBlock, lds, s>>>(Tc, p->build_R, p->build_L, p->nb_vis, nb_pri, nb_ine);
+    else
+      k_update_visual<K><<<p->nb_vis + T.n_norm_part + nb_pri + nb_ine, kBlock, lds, s>>>(T, p->build_R, p->build_L, p->nb_vis, nb_pri, nb_ine);
     if (T.n_pri && !merged) k_cost_prior<K><<<p->nb_pri, kBlock, cp_lds_bytes(p), s>>>(T, T.cp_cand, T.cand_part + p->nb_vis);
     if (T.n_ine && !merged)
       k_cost_inertial<K, 4><<<p->nb_ine, kInertialBlock, cp_lds_bytes(p), s>>>(T, T.cp_cand, T.bias_g_cand, T.bias_a_cand, T.gravity_cand,
                                                                           T.cand_part + p->nb_vis + p->nb_pri);
-  } else
-    k_backsub_retract<<<T.n_lm_part + T.n_norm_part, kBlock, 0, s>>>(T);
+  } else if (T.nc)
+    k_backsub_retract<true><<<T.n_lm_part + T.n_norm_part, kBlock, 0, s>>>(T);
+  else
+    k_backsub_retract<false><<<T.n_lm_part + T.n_norm_part, kBlock, 0, s>>>(T);
   if (p->fused) {
   } else if (linearize_candidate) {
     if (lin_events) HIP_TRY(hipEventRecord(lin_events[0], s));  // stage timing: this launch is booked under "linearise", not "update"
     k_linearize_visual<K><<<p->nb_vis, lin_block<K>(), lin_lds_bytes<K>(p), s>>>(T, nullptr, T.v_pos, 1, T.cand_part, nullptr, T.cp_cand, T.lm_cand);
     if (lin_events) HIP_TRY(hipEventRecord(lin_events[1], s));
   } else if ((T.n_ine || T.n_pri) && !(T.debug_flags & 33554432)) {  // one launch for all factor types (A/B switch 33554432: one per type)
-    k_cost_all<K, 4><<<p->nb_vis + p->nb_pri + p->nb_ine, kBlock, cp_lds_bytes(p), s>>>(T, T.cp_cand, T.lm_cand, T.bias_g_cand, T.bias_a_cand, T.gravity_cand,
+    k_cost_all<K, 4><<<p->nb_vis + p->nb_pri + p->nb_ine, kBlock, cp_lds_bytes(p), s>>>(Tc, T.cp_cand, T.lm_cand, T.bias_g_cand, T.bias_a_cand, T.gravity_cand,
                                                                                        T.cand_part, p->nb_vis, p->nb_pri);
   } else {
-    if (T.n_vis) k_cost_visual<K><<<p->nb_vis, kBlock, cp_lds_bytes(p), s>>>(T, T.cp_cand, T.lm_cand, T.cand_part);
+    if (T.n_vis) k_cost_visual<K><<<p->nb_vis, kBlock, cp_lds_bytes(p), s>>>(Tc, T.cp_cand, T.lm_cand, T.cand_part);
     if (T.n_pri) k_cost_prior<K><<<p->nb_pri, kBlock, cp_lds_bytes(p), s>>>(T, T.cp_cand, T.cand_part + p->nb_vis);
     if (T.n_ine)
       k_cost_inertial<K, 4><<<p->nb_ine, kInertialBlock, cp_lds_bytes(p), s>>>(T, T.cp_cand, T.bias_g_cand, T.bias_a_cand, T.gravity_cand,
                                                                           T.cand_part + p->nb_vis + p->nb_pri);
   }
   if (fold_next) return HS_OK;  // (fold_decision_into_build: the next iteration's k_build_visual decides, launch_build(..., fold = true))
-  k_pack_decision<<<1, kBlock, 0, s>>>(T, decide_here);
+  k_pack_decision<<<1, kBlock, 0, s>>>(Td, decide_here);
   HIP_TRY(hipGetLastError());
   const int rc = exchange(p, T.xbuf + T.xo_dec, 5);  // candidate cost + norms + landmark-side model-cost terms
   if (rc) return rc;
@@ -652,6 +669,7 @@ int launch_update(hs_problem* p, bool linearize_candidate = false, bool deferred
   // (deferred: speculative solves of larger problems — the next iteration's k_backsub_retract copies the accepted candidate to x on its way,
   //  hs_solve launches k_commit once behind the last iteration)
   if (!inline_commit && !deferred_commit) k_commit<<<nb_commit, kBlock, 0, s>>>(T);
+  if (T.nc) k_calib_commit<<<1, kBlock, 0, s>>>(T, p->d_cam.p, p->d_cam_cand.p);  // an accepted step: cam <- candidate cameras
   HIP_TRY(hipGetLastError());
   return HS_OK;
 }
@@ -696,7 +714,7 @@ static void warm_kernels(int device) {
       reinterpret_cast<const void*>(&k_border_forward2),
       reinterpret_cast<const void*>(&k_border_schur), reinterpret_cast<const void*>(&k_border_solve), reinterpret_cast<const void*>(&k_border_solve_reg<3>), reinterpret_cast<const void*>(&k_border_solve_reg<4>),
       reinterpret_cast<const void*>(&k_border_solve_reg<5>), reinterpret_cast<const void*>(&k_border_solve_reg<6>), reinterpret_cast<const void*>(&k_border_solve_reg<7>),
-      reinterpret_cast<const void*>(&k_border_solve_reg<8>), reinterpret_cast<const void*>(&k_border_apply), reinterpret_cast<const void*>(&k_backsub_retract),
+      reinterpret_cast<const void*>(&k_border_solve_reg<8>), reinterpret_cast<const void*>(&k_border_apply), reinterpret_cast<const void*>(&k_backsub_retract<false>),
       reinterpret_cast<const void*>(&k_pack_decision), reinterpret_cast<const void*>(&k_decide), reinterpret_cast<const void*>(&k_commit),
       reinterpret_cast<const void*>(&k_reset_state), reinterpret_cast<const void*>(&k_scatter_uploads)};
   for (const void* k : kernels) (void)hipFuncGetAttributes(&fa, k);
@@ -721,6 +739,7 @@ int set_func_attributes(hs_problem* p) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gram_pair<K, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_build_visual<K>), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_visual<K>), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_visual<K, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_linearize_visual<K>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   });
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dense_solve_mx), hipFuncAttributeMaxDynamicSharedMemorySize, int(kDxLdsDoubles * sizeof(double))));

@@ -232,6 +232,8 @@ struct hs_problem {
   int n_cam = 0;
   std::vector<double> cam;  // n x 16
   std::vector<uint8_t> cam_const;  // hs_set_camera_constancy: n x 3 [T_bs, intrinsics, distortion]; empty: every block constant (camera.hpp:18)
+  bool cam_estimation = false;     // hs_set_camera_estimation: hs_solve estimates the free blocks (off: it refuses a handle that has one)
+  std::vector<double> cam_snap;    // hs_snapshot: the camera table (host copy; hs_solve keeps `cam` equal to the device table)
   int n_sensor = 0;
   std::vector<double> sensor;  // n x 8
   int n_lm = 0;
@@ -328,7 +330,8 @@ struct hs_problem {
   int nc = 0;                    // free camera coordinates in the system (camera_columns)
   std::vector<int> calib_map;    // nc: camera << 8 | column inside the camera's 14
   DBuf<int> d_calib_map;
-  DBuf<double> d_calib_rec, d_calib_Yc, d_calib_part;
+  DBuf<double> d_calib_rec, d_calib_Yc, d_calib_part, d_cam_cand;
+  DBuf<int> d_calib_bfwd;        // all-zero Tables::bfwd_start of a handle with free camera coordinates: a camera column is dense, no row of it is skipped
   std::vector<hipEvent_t> events;
   hipStream_t side = nullptr;           // second stream: the segment partials run next to the landmark pass (independent inputs)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_irec = nullptr;
@@ -714,28 +717,40 @@ int prepare(hs_problem* p) {
   HIP_TRY(p->d_ch_gmax.reserve(size_t(p->nb_vis) + 1));
   HIP_TRY(p->d_cand_part.reserve(p->nb_vis + p->nb_pri + p->nb_ine + 1));
   const int nb_norm = p->nb_cp;
-  HIP_TRY(p->d_norm_part.reserve(2 * size_t(nb_norm)));
+  HIP_TRY(p->d_norm_part.reserve(2 * size_t(nb_norm) + 2));  // (+ the camera blocks' pair, k_calib_candidate)
   p->nc = camera_columns(p, &p->calib_map);
   if (p->nc > kCalibMaxCols)
     HS_FAIL(HS_ERR_INVALID, "too many free camera coordinates: at most " + std::to_string(kCalibMaxCols) + " per window (kCalibMaxCols), " +
                                 std::to_string(p->nc) + " requested (hs_set_camera_constancy)");
   const int nbi = p->has_imu ? 6 * p->n_bias + 2 : 0;  // bias splines + gravity
   const int nbd = nbi + p->nc;                          // border unknowns: those, then the free camera coordinates
-  // (the two limits below belong to the solver's bordered factorisation — k_border_forward, k_border_solve —, which a handle with free camera
-  //  coordinates does not reach in this version (hs_solve refuses it): they count the bias / gravity columns only)
+  // (the two limits below belong to the solver's bordered factorisation — k_border_forward, k_border_solve. A handle that only BUILDS the system
+  //  of its free camera coordinates (hs_reduced_system) never reaches them: they count the bias / gravity columns, and the camera columns too
+  //  once hs_set_camera_estimation sends them through hs_solve)
+  if (p->nc && p->cam_estimation) {
+    if (size_t(np) * 8 * 8 > 150 * 1024)
+      HS_FAIL(HS_ERR_INVALID, "window too long for the LDS-resident border forward sweep with free camera coordinates: " + std::to_string(p->n_cp) +
+                                  " control points, at most " + std::to_string(150 * 1024 / (6 * 8 * 8)) + " (6 n_cp x 8 doubles within 150 KiB)");
+    if (nbd + 1 > 128 && (size_t(nbd + 1) * (nbd + 1) + nbd) * sizeof(double) > size_t(150) * 1024)
+      HS_FAIL(HS_ERR_INVALID, "too many border unknowns for the LDS-resident dense solve of the border system: " + std::to_string(nbi) +
+                                  " bias / gravity + " + std::to_string(p->nc) + " free camera coordinates = " + std::to_string(nbd) +
+                                  ", at most 137 (hs_set_camera_estimation)");
+  }
   if (nbi && size_t(np) * 8 * 8 > 150 * 1024) HS_FAIL(HS_ERR_INVALID, "window too long for the LDS-resident border forward sweep");
   // (k_border_solve: the border Schur complement, augmented, in LDS — (nb + 1)^2 + nb doubles within the 150 KB the kernel may ask for: nb <= 137,
   //  i.e. 22 bias control points; the launch used to fail inside hs_solve with "invalid argument")
   if (nbi + 1 > 128 && (size_t(nbi + 1) * (nbi + 1) + nbi) * sizeof(double) > size_t(150) * 1024)
     HS_FAIL(HS_ERR_INVALID, "too many border unknowns (bias control points) for the LDS-resident dense solve of the border system: at most 22 bias control points per window");
   const int x_count0 = np * (ncb + 3) + np * nbd + nbd * nbd + nbd + 1 + p->world;
-  const int x_count1 = x_count0 + p->nc;  // (+ diag(J'J) of the camera columns)
+  const int x_count1 = x_count0 + 2 * p->nc;  // (+ diag(J'J) and the full gradient C'r of the camera columns)
   if (p->nc) {
     HIP_TRY(p->d_calib_map.upload(p->calib_map, s));
     HIP_TRY(p->d_calib_rec.reserve(size_t(std::max(n_vis, 1)) * (40 + 12 * k)));
     HIP_TRY(p->d_calib_Yc.reserve(size_t(std::max(p->n_lm, 1)) * 3 * p->nc));
     const int n_parts = (n_vis + kCalibRowChunk - 1) / kCalibRowChunk + (p->n_lm + kCalibLmChunk - 1) / kCalibLmChunk;
     HIP_TRY(p->d_calib_part.reserve(size_t(std::max(n_parts, 1)) * (p->nc * p->nc + 2 * p->nc)));
+    HIP_TRY(p->d_cam_cand.reserve(size_t(kCamStride) * std::max(p->n_cam, 1)));
+    HIP_TRY(p->d_calib_bfwd.upload(std::vector<int>((nbd + kBorderCols - 1) / kBorderCols + kSchurTile, 0), s));
   }
   HIP_TRY(p->d_ybuf.reserve(np));
   HIP_TRY(p->d_scale_b.reserve(nbd + 1));
@@ -887,7 +902,7 @@ int prepare(hs_problem* p) {
     T.Sb2 = need ? p->d_Sb2.p : nullptr, T.g2 = need ? p->d_g2.p : nullptr;
   }
   T.scale_b = p->d_scale_b.p, T.Spb = p->d_Spb.p, T.Sbb = p->d_Sbb.p, T.gb_s = p->d_gb_s.p, T.D2b = p->d_D2b.p;
-  T.Zb = p->d_Zb.p, T.Cb = p->d_Cb.p, T.hb = p->d_hb.p, T.xb = p->d_xb.p, T.delta_b = p->d_delta_b.p, T.i_bias_ptr = p->d_i_bias_ptr.p, T.bfwd_start = p->d_bfwd_start.p;
+  T.Zb = p->d_Zb.p, T.Cb = p->d_Cb.p, T.hb = p->d_hb.p, T.xb = p->d_xb.p, T.delta_b = p->d_delta_b.p, T.i_bias_ptr = p->d_i_bias_ptr.p, T.bfwd_start = p->nc ? p->d_calib_bfwd.p : p->d_bfwd_start.p;
   T.x_count1 = x_count1, T.xo_dec = x_count1, T.xo_cdj = x_count0;
   T.fused = p->fused ? 1 : 0, T.n_chunk = p->fused ? p->n_group_wg : 0, T.ch_ptr = p->d_ch_ptr.p, T.ch_desc = p->d_ch_desc.p;
   T.build_stream_lg = p->fused ? build_streams_packed(vs.bw, k) : 0;

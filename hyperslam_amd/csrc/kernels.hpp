@@ -15,6 +15,8 @@
 //   k_backsub_retract                        step for landmarks, candidate point = Plus(x, delta), norm / model-cost partials
 //   k_cost_visual / _prior / _inertial       cost at the candidate point
 //   k_pack_decision -> [all-reduce] -> k_decide -> k_commit      trust-region logic and acceptance
+// Handles with free camera coordinates (kernels_calib.hpp) add k_calib_rows / _landmark / _pc / _cc / _finish behind the landmark factors,
+// k_calib_candidate in front of the update (whose <true> instantiations carry the Y_c dc term) and k_calib_commit behind the decision.
 #pragma once
 #include "kernels_common.hpp"
 #include "kernels_linearize.hpp"

@@ -334,7 +334,8 @@ HSD void finalize_border_body(const Tables& T, const int wg, const int n_wg, con
           T.dense[size_t(ii) * kDenseLd + n_dense] = sr * g, T.dense[size_t(n_dense) * kDenseLd + ii] = sr * g;
         }
         if (fresh) T.scale_b[b] = sr;
-        T.gabs[T.np + b] = fabs(g);
+        // (camera columns: g_b holds their REDUCED gradient; the gradient tolerance test takes the full one, C'r, kept behind diag(J'J)_c)
+        T.gabs[T.np + b] = fabs(b < nbi ? g : X[T.xo_cdj + T.nc + (b - nbi)]);
       }
       T.Sbb[size_t(b) * nb + c] = out;
       if (T.dense) T.dense[size_t(np - 6 * T.dense_f0 + b) * kDenseLd + (np - 6 * T.dense_f0 + c)] = out;

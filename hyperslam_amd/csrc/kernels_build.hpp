@@ -836,7 +836,7 @@ HSD void update_cost_workgroup(const Tables& T, int blk, int nb_pri, int n_vis_p
   double* ba = bg + 4 * T.n_bias;
   double* grav = ba + 4 * T.n_bias;
   for (int j = tid; j < T.sp.n_cp; j += kBlock) candidate_control_point(T, j, cps + 8 * j);
-  if (T.nb > 0) {
+  if (T.nb > T.nc) {  // (bias points and gravity: with an IMU only — a border of free camera coordinates alone has neither)
     for (int b = tid; b < 2 * T.n_bias; b += kBlock) candidate_bias_point(T, b, bg + 4 * b);  // (ba follows bg: b >= n_bias lands there)
     if (tid == 0) sphere_plus(T.gravity, T.delta_b + 6 * T.n_bias, grav);
   }
@@ -859,7 +859,9 @@ HSD void update_cost_workgroup(const Tables& T, int blk, int nb_pri, int n_vis_p
 }
 
 /// One workgroup of the update launch; false: the solve had ended before (nothing done).
-template <int K>
+/// CALIB (handles with free camera coordinates, T.nc > 0): the back-substitution of a landmark gains the camera term - Y_c,l y_c (kernels_calib.hpp);
+/// the launch passes the candidate camera table as T.cam, so the candidate cost is evaluated with it.
+template <int K, bool CALIB = false>
 HSD bool update_visual_workgroup(const Tables& T, int R, int Lmax, int n_vis_parts, int nb_pri, double* smem) {
   const int w = blockIdx.x, tid = threadIdx.x;
   DevState* st = T.st;
@@ -886,7 +888,7 @@ HSD bool update_visual_workgroup(const Tables& T, int R, int Lmax, int n_vis_par
         for (int c = 0; c < 8; ++c) xs = fma(x[c], x[c], xs), ss = fma(x[c] - y[c], x[c] - y[c], ss);
       }
     }
-    if (T.nb > 0) {  // border unknowns (replicated like the control points): bias control points [x y z t] and gravity
+    if (T.nb > T.nc) {  // (bias points and gravity: with an IMU only — a border of free camera coordinates alone has neither)  // border unknowns (replicated like the control points): bias control points [x y z t] and gravity
       for (int b = j; b < 2 * T.n_bias; b += T.n_norm_part * blockDim.x) {
         const bool acc = b >= T.n_bias;
         const int bi = acc ? b - T.n_bias : b;
@@ -1015,6 +1017,9 @@ HSD bool update_visual_workgroup(const Tables& T, int R, int Lmax, int n_vis_par
     const int l = tid, dl = lo + l;
     double t0 = 0.0, t1 = 0.0, t2 = 0.0;
     for (int jb = 0; jb < l_ncp[l]; ++jb) t0 += part[4 * (l * bw + jb)], t1 += part[4 * (l * bw + jb) + 1], t2 += part[4 * (l * bw + jb) + 2];
+    if constexpr (CALIB) {
+      for (int c = 0; c < T.nc; ++c) calib_backsub_term(T, dl, c, &t0, &t1, &t2);
+    }
     const double z0 = yh[0] - t0, z1 = yh[1] - t1, z2 = yh[2] - t2;  // L' y = z
     const double y2 = z2 / L[5], y1 = (z1 - L[4] * y2) / L[2], y0 = (z0 - L[1] * y1 - L[3] * y2) / L[0];
     const double s[3] = {active ? -y0 : 0.0, active ? -y1 : 0.0, active ? -y2 : 0.0};
@@ -1070,10 +1075,10 @@ HSD bool update_visual_workgroup(const Tables& T, int R, int Lmax, int n_vis_par
 /// (Round 6 also let the workgroup that finishes LAST take the trust-region decision — every workgroup releases its partials and draws a ticket —
 ///  to save k_pack_decision's launch: an agent-scope release writes the XCD's L2 back, and ~150 of them made the launch 16 us longer (45 us from
 ///  every wave) where the one-workgroup launch behind it costs 5.5. Measured on the replays, not kept: a kernel boundary does that once.)
-template <int K>
+template <int K, bool CALIB = false>
 __global__ void __launch_bounds__(kBlock) k_update_visual(Tables T, int R, int Lmax, int n_vis_parts, int nb_pri = 0, int nb_ine = 0) {
   HS_DYNAMIC_LDS(smem);
-  update_visual_workgroup<K>(T, R, Lmax, n_vis_parts, nb_pri, smem);
+  update_visual_workgroup<K, CALIB>(T, R, Lmax, n_vis_parts, nb_pri, smem);
 }
 
 }  // namespace hs

@@ -159,19 +159,75 @@ __global__ void __launch_bounds__(kBlock) k_calib_cc(Tables T, int n_row_chunks)
 
 /// One thread per entry: the partials of k_calib_cc in workgroup order into the camera block of the exchange buffer (H_bb, g_b) and
 /// diag(J'J)_c (Tables::xo_cdj). The cross block bias / gravity x camera is zero (k_border_pb's zero fill, or no IMU).
-__global__ void __launch_bounds__(kBlock) k_calib_finish(Tables T, int n_parts) {
+/// n_row_chunks >= 0: the sum of the row partials alone, C'r — the FULL gradient of the camera columns, which the gradient tolerance test and the
+/// model cost change take (g_b holds the reduced one) — goes behind the diagonal, T.xbuf[T.xo_cdj + nc ..].
+__global__ void __launch_bounds__(kBlock) k_calib_finish(Tables T, int n_parts, int n_row_chunks = -1) {
   if (T.st->done) return;
   const int nc = T.nc, E = nc * nc + 2 * nc, nb = T.nb, nbi = T.nb - T.nc;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= E) return;
-  double s = 0.0;
-  for (int w = 0; w < n_parts; ++w) s += T.calib_part[size_t(w) * E + e];
+  double s = 0.0, rows = 0.0;
+  for (int w = 0; w < n_parts; ++w) {
+    s += T.calib_part[size_t(w) * E + e];
+    if (w + 1 == n_row_chunks) rows = s;
+  }
   if (e < nc * nc)
     T.xbuf[T.xo_bb + size_t(nbi + e / nc) * nb + nbi + e % nc] = s;
-  else if (e < nc * nc + nc)
+  else if (e < nc * nc + nc) {
     T.xbuf[T.xo_gb + nbi + e - nc * nc] = s;
-  else
+    if (n_row_chunks >= 0) T.xbuf[T.xo_cdj + nc + e - nc * nc] = rows;
+  } else
     T.xbuf[T.xo_cdj + e - nc * nc - nc] = s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Solve side (hs_set_camera_estimation): the candidate camera table and the commit of an accepted step. Both are one-workgroup launches
+// of their own on handles with free camera coordinates; handles without launch neither.
+// ---------------------------------------------------------------------------------------------------------------------
+
+/// Candidate cameras from the unscaled border step dc = T.delta_b[nb - nc ..]: cam_cand (n_cam x 16, a table next to T.cam that only the
+/// launches of a handle with free camera coordinates know: Tables keeps the layout every other kernel was compiled for) = T.cam with every free block retracted — T_bs on
+/// Product(EigenQuaternion, R3) (q <- dq(d_rot) (x) q, p <- p + d_trans), intrinsics and distortion Euclidean. One lane per camera column
+/// (nc <= kCalibMaxCols); the lane of a T_bs block's first column retracts the block. Also the camera blocks' share of the decision:
+///   T.norm_part[2 norm_slot ..] = (|x|^2, |x+ - x|^2) over the ambient coordinates of the free blocks (Ceres' x_norm / step_norm), and
+///   DevState::g_dot_step_far    = (g_c - g_c,reduced) . dc: the step outputs of the border sweeps form g . step with T.gb_s, which holds the
+///                                 REDUCED gradient on the camera columns; the model cost change takes the full one (C'r, k_calib_finish).
+///                                 One-ended solves leave this slot zero, and a handle with free cameras is always solved one-ended.
+__global__ void __launch_bounds__(kBlock) k_calib_candidate(Tables T, double* cam_cand, int norm_slot) {
+  if (T.st->done) return;
+  __shared__ double red[3 * (kBlock / 64)];
+  const int tid = threadIdx.x, nc = T.nc, nbi = T.nb - T.nc;
+  for (int e = tid; e < kCamStride * T.n_cam; e += kBlock) cam_cand[e] = T.cam[e];
+  __syncthreads();
+  double v[3] = {0.0, 0.0, 0.0};  // |x|^2, |x+ - x|^2, (g - g_reduced) . step
+  if (tid < nc) {
+    const int m = T.calib_map[tid], col = m & 0xff;
+    const double* x = T.cam + kCamStride * (m >> 8);
+    double* y = cam_cand + kCamStride * (m >> 8);
+    const double* d = T.delta_b + nbi + tid;
+    if (col == 0) {  // T_bs: its six columns are consecutive
+      const Quat q = quat_plus(Quat{x[0], x[1], x[2], x[3]}, V3{d[0], d[1], d[2]});
+      y[0] = q.x, y[1] = q.y, y[2] = q.z, y[3] = q.w, y[4] = x[4] + d[3], y[5] = x[5] + d[4], y[6] = x[6] + d[5];
+#pragma unroll
+      for (int c = 0; c < 7; ++c) v[0] = fma(x[c], x[c], v[0]), v[1] = fma(y[c] - x[c], y[c] - x[c], v[1]);
+    } else if (col >= 6) {  // intrinsics [cx cy fx fy] at 7 .., distortion [k1 k2 p1 p2] at 11 ..
+      const double xv = x[1 + col], yv = xv + d[0];
+      y[1 + col] = yv;
+      v[0] = xv * xv, v[1] = (yv - xv) * (yv - xv);
+    }
+    v[2] = (T.xbuf[T.xo_cdj + nc + tid] - T.xbuf[T.xo_gb + nbi + tid]) * d[0];
+  }
+  block_sum_n<3>(v, red);
+  if (tid == 0) {
+    T.norm_part[2 * norm_slot] = v[0], T.norm_part[2 * norm_slot + 1] = v[1];
+    T.st->g_dot_step_far = v[2];
+  }
+}
+
+/// cam <- candidate when the step was accepted (k_commit's rule: `accepted` is read even when a convergence test just ended the solve).
+__global__ void __launch_bounds__(kBlock) k_calib_commit(Tables T, double* cam, const double* cam_cand) {
+  if (!T.st->accepted) return;
+  for (int e = threadIdx.x; e < kCamStride * T.n_cam; e += kBlock) cam[e] = cam_cand[e];
 }
 
 }  // namespace hs

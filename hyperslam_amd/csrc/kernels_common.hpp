@@ -147,4 +147,12 @@ HSD void stage_cps(const double* __restrict__ src, double* dst, int n_doubles) {
   __syncthreads();
 }
 
+/// Free camera coordinates (kernels_calib.hpp; T.nc > 0, the update kernels' CALIB instantiations). The camera term of the landmark back-substitution for camera column c of landmark dl: Y_c[u][c] * y_c, u = 0 .. 2, with y_c = -dc (the
+/// solution of the normal equations, as y_p = -step_p):  L' y_l = yh - Yh' (Sp o y_p) - Y_c y_c.
+HSD void calib_backsub_term(const Tables& T, int dl, int c, double* t0, double* t1, double* t2) {
+  const double* Yc = T.calib_Yc + size_t(dl) * 3 * T.nc + c;
+  const double yc = -T.delta_b[T.nb - T.nc + c];
+  *t0 = fma(Yc[0], yc, *t0), *t1 = fma(Yc[T.nc], yc, *t1), *t2 = fma(Yc[2 * T.nc], yc, *t2);
+}
+
 }  // namespace hs

@@ -10,7 +10,10 @@ namespace hs {
 // with the landmark-side terms of the decision (|x|^2, |x - x+|^2, g.step, step'D^2 step) summed per workgroup in a fixed
 // order. Workgroups [n_lm_part, n_lm_part + n_norm_part): candidate control points / bias points / gravity = Plus(x, delta) per
 // Ceres manifold (quaternion left-multiplicative, R^3 additive, stamp constant, sphere) and their norms.
+// CALIB (handles with free camera coordinates, T.nc > 0): the back-substitution gains the camera term, y_l = L^-T (yh_l - Yh_l' (Sp o y_p) -
+// Y_c,l y_c) with y_c = -dc, one lane per camera column in front of the wave sum. The candidate cameras and their norms: k_calib_candidate.
 // ---------------------------------------------------------------------------------------------------------------------
+template <bool CALIB = false>
 __global__ void __launch_bounds__(kBlock) k_backsub_retract(Tables T) {
   if (T.st->done) return;
   __shared__ double red[kBlock / 64][4];
@@ -51,6 +54,9 @@ __global__ void __launch_bounds__(kBlock) k_backsub_retract(Tables T) {
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) t0 = fma(yv[u][0], yp[u], t0), t1 = fma(yv[u][1], yp[u], t1), t2 = fma(yv[u][2], yp[u], t2);
+      }
+      if constexpr (CALIB) {
+        if (lane < T.nc) calib_backsub_term(T, dl, lane, &t0, &t1, &t2);
       }
       t0 = wave_sum(t0), t1 = wave_sum(t1), t2 = wave_sum(t2);
       if (lane == 0) {
@@ -107,7 +113,7 @@ __global__ void __launch_bounds__(kBlock) k_backsub_retract(Tables T) {
     }
   }
   // border unknowns (replicated like the control points): bias control points [x y z t] and gravity
-  if (T.nb > 0) {
+  if (T.nb > T.nc) {  // (bias points and gravity: with an IMU only — a border of free camera coordinates alone has neither)
     for (int b = j; b < 2 * T.n_bias; b += T.n_norm_part * blockDim.x) {
       const bool acc = b >= T.n_bias;
       const int bi = acc ? b - T.n_bias : b;
@@ -397,7 +403,7 @@ HSD void commit_body(const Tables& T, const int idx, const int stride) {
   };
   copy(T.cp, T.cp_cand, 8 * T.sp.n_cp);
   copy(T.lm, T.lm_cand, 3 * T.n_lm);
-  if (T.nb > 0) {
+  if (T.nb > T.nc) {  // (bias points and gravity: with an IMU only — a border of free camera coordinates alone has neither)
     for (int e = idx; e < 4 * T.n_bias; e += stride) T.bias_g[e] = T.bias_g_cand[e], T.bias_a[e] = T.bias_a_cand[e];
     if (idx < 3) T.gravity[idx] = T.gravity_cand[idx];
   }

@@ -365,6 +365,12 @@ class Problem:
         c = _arr(constant, np.uint8, (-1, 3))
         self._check(self.lib.set_camera_constancy(self.h, c.shape[0], _u8(c)), "set_camera_constancy")
 
+    def set_camera_estimation(self, enabled=True):
+        """solve() estimates the free camera blocks of set_camera_constancy on this handle (off by default: solve() refuses them)."""
+        if not hasattr(self.lib, "set_camera_estimation"):
+            raise HsError(f"{self.lib.prefix}set_camera_estimation: not provided by this library (sensor blocks are constant there)")
+        self._check(self.lib.set_camera_estimation(self.h, int(bool(enabled))), "set_camera_estimation")
+
     def cameras(self):
         """Current camera values (T_bs (n, 7), intrinsics (n, 4), distortion (n, 4)) in the layout of the window's tables."""
         n = len(_arr(self.window.cam_T_bs, _f64, (-1, 7)))

@@ -135,9 +135,17 @@ int hs_set_cameras(hs_problem* p, int n, const double* T_bs, const double* intri
  * table order the free blocks [T_bs 6 | intrinsics 4 | distortion 4], Ceres-local: T_bs on HS_MANIFOLD_SE3 [d_rot(3) d_trans(3)],
  * intrinsics [cx cy fx fy] and radtan [k1 k2 p1 p2] Euclidean. Pixel residuals touch all three blocks of their camera, bearing residuals
  * T_bs only (their intrinsics / distortion columns are zero). A camera no visual residual references is left out. At most 64 free camera
- * coordinates per window (HS_ERR_INVALID from the call that prepares the tables). In this version hs_solve and hs_compute_covariance
- * refuse a handle with free camera coordinates (HS_ERR_STATE), and so does hs_reduced_system on a sharded handle (world > 1). */
+ * coordinates per window (HS_ERR_INVALID from the call that prepares the tables). hs_solve estimates the free blocks once
+ * hs_set_camera_estimation has enabled it on the handle; by default it refuses a handle with free camera coordinates (HS_ERR_STATE).
+ * hs_compute_covariance refuses such a handle (HS_ERR_STATE), and so do hs_solve and hs_reduced_system on a sharded one (world > 1). */
 int hs_set_camera_constancy(hs_problem* p, int n, const uint8_t* constant);
+/* hs_solve estimates the free camera blocks of hs_set_camera_constancy on this handle (enabled != 0). Off by default: hs_solve then refuses
+ * a handle with free camera coordinates exactly as before (HS_ERR_STATE). An accepted step moves the camera table like every other variable:
+ * hs_get_cameras, hs_cost, hs_linearize, hs_reduced_system, hs_process_tracks and hs_sample_trajectory see the estimate, hs_snapshot /
+ * hs_restore cover it, hs_set_cameras overrides it. Such a window is solved one-ended with the camera coordinates as border columns; the border
+ * (bias / gravity + camera coordinates) is limited to 137 unknowns and the window to 400 control points (HS_ERR_INVALID from the call that
+ * prepares the tables, naming the limit). Handles without a free camera coordinate are not affected by the switch. DESIGN.md section 13. */
+int hs_set_camera_estimation(hs_problem* p, int enabled);
 /* Current camera values in the layout of hs_set_cameras (n x 7, n x 4, n x 4). Each pointer may be NULL. */
 int hs_get_cameras(hs_problem* p, double* T_bs, double* intrinsics, double* distortion);
 /* Plain sensors (extrinsics only) used by pose-prior factors (manifold.cpp:30-33). T_bs n x 7. */
