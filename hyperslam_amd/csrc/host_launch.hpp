@@ -463,8 +463,8 @@ int launch_factor(hs_problem* p) {
     }
     Tables T3 = T2;
     T3.join_epoch = ++p->join_epoch;
-    const BackJob j0{T.Ub, T.Ubk, T.ybuf, p->d_Vb.p, p->d_yt.p, m + w_mid, 0, 0};
-    const BackJob j1{p->d_Ub2.p, p->d_Ubk2.p, p->d_ybuf2.p, p->d_Vb2.p, p->d_yt2.p, mB, w_mid, 1};
+    const BackJob j0{T.Ub, T.Ubk, T.ybuf, p->d_Vb.p, p->d_yt.p, m + w_mid, 0, 0, p->d_Mb.p};
+    const BackJob j1{p->d_Ub2.p, p->d_Ubk2.p, p->d_ybuf2.p, p->d_Vb2.p, p->d_yt2.p, mB, w_mid, 1, p->d_Mb2.p};
     // (the two older sweeps are kept as measurement switches for visual-only systems, the shape they were measured on; they do not write
     //  the border's step outputs)
     const bool sweep_w = HS_AB(T.debug_flags, 65536) && !T.nb && p->vb_len == size_t(T.np) * (6 * T.bw),  // (its pad of zeros sits right behind np x ncb)
@@ -479,10 +479,15 @@ int launch_factor(hs_problem* p) {
         k_band_backward2<<<2, kCholThreads, 2 * size_t(T.np) * sizeof(double) + g_lds, s>>>(T3, j0, j1, m);
       else
 #endif
-        // super-blocks of four block rows; the inverses of the diagonal super-blocks come from extra workgroups of the launch
-        k_band_backward_sb<<<2 + (m + w_mid + kSb - 1) / kSb + (mB + kSb - 1) / kSb, kCholThreads,
-                             std::max((2 * size_t(T.np) + 32) * sizeof(double) + g_lds + sb_phase_a_doubles(T.bw) * sizeof(double),
-                                      size_t(3 * kSbN * (kSbN + 1)) * sizeof(double)), s>>>(T3, j0, j1, m, 2, 0);
+      {  // super-blocks of four block rows; the inverses of the diagonal super-blocks come from extra workgroups of the launch
+        const unsigned n_wg = 2 + (m + w_mid + kSb - 1) / kSb + (mB + kSb - 1) / kSb;
+        const size_t lds = std::max((2 * size_t(T.np) + 32) * sizeof(double) + g_lds + sb_phase_a_doubles(T.bw) * sizeof(double),
+                                    size_t(3 * kSbN * (kSbN + 1)) * sizeof(double));
+        if (6 * (T.bw - 1) <= 96 && !(T.debug_flags2 & 1))  // one phase per super-step on premultiplied blocks (A/B switch 4294967296: two phases)
+          k_band_backward_pm<<<n_wg, kCholThreads, lds, s>>>(T3, j0, j1, m, 2, 0);
+        else
+          k_band_backward_sb<<<n_wg, kCholThreads, lds, s>>>(T3, j0, j1, m, 2, 0);
+      }
     } else {
 #if HS_PROFILE_HOOKS
       launch_backward_w(T3, j0, j1, m, 2, s);
@@ -561,9 +566,13 @@ int launch_factor(hs_problem* p) {
     if (6 * (T.bw - 1) <= 96 && !(T.debug_flags & 268435456)) {  // super-blocks of four block rows: one lane pair per pending row, 96 pairs
       Tables T3 = T;
       T3.join_epoch = ++p->join_epoch;
-      const BackJob j0{T.Ub, T.Ubk, T.ybuf, p->d_Vb.p, p->d_yt.p, T.np / 6, 0, 0};
-      k_band_backward_sb<<<1 + (T.np / 6 + kSb - 1) / kSb, kCholThreads,
-                           std::max((2 * size_t(T.np) + 32) * sizeof(double), size_t(3 * kSbN * (kSbN + 1)) * sizeof(double)), s>>>(T3, j0, j0, -1, 1, f0);
+      const BackJob j0{T.Ub, T.Ubk, T.ybuf, p->d_Vb.p, p->d_yt.p, T.np / 6, 0, 0, p->d_Mb.p};
+      const unsigned n_wg = 1 + (T.np / 6 + kSb - 1) / kSb;
+      const size_t lds = std::max((2 * size_t(T.np) + 32) * sizeof(double), size_t(3 * kSbN * (kSbN + 1)) * sizeof(double));
+      if (!(T.debug_flags2 & 1))  // (A/B switch 4294967296: two phases per super-step)
+        k_band_backward_pm<<<n_wg, kCholThreads, lds, s>>>(T3, j0, j0, -1, 1, f0);
+      else
+        k_band_backward_sb<<<n_wg, kCholThreads, lds, s>>>(T3, j0, j0, -1, 1, f0);
     } else {  // wide bands (long feature tracks): one block row per step, one lane per pending row
       k_band_backward<<<1, kCholThreads, 2 * size_t(T.np) * sizeof(double), s>>>(T, f0);
     }
@@ -710,7 +719,7 @@ static void warm_kernels(int device) {
       reinterpret_cast<const void*>(&k_finalize_border), reinterpret_cast<const void*>(&k_reduce_partials), reinterpret_cast<const void*>(&k_factor_decoupled_rows),
       reinterpret_cast<const void*>(&k_dense_factor), reinterpret_cast<const void*>(&k_dense_solve_mx), reinterpret_cast<const void*>(&k_band_factor_wide), reinterpret_cast<const void*>(&k_band_factor<1>),
       reinterpret_cast<const void*>(&k_band_factor<2>), reinterpret_cast<const void*>(&k_band_factor_la<1, 3>), reinterpret_cast<const void*>(&k_band_factor_la<1, 4>),
-      reinterpret_cast<const void*>(&k_band_backward), reinterpret_cast<const void*>(&k_band_backward_sb), reinterpret_cast<const void*>(&k_border_forward),
+      reinterpret_cast<const void*>(&k_band_backward), reinterpret_cast<const void*>(&k_band_backward_sb), reinterpret_cast<const void*>(&k_band_backward_pm), reinterpret_cast<const void*>(&k_border_forward),
       reinterpret_cast<const void*>(&k_border_forward2),
       reinterpret_cast<const void*>(&k_border_schur), reinterpret_cast<const void*>(&k_border_solve), reinterpret_cast<const void*>(&k_border_solve_reg<3>), reinterpret_cast<const void*>(&k_border_solve_reg<4>),
       reinterpret_cast<const void*>(&k_border_solve_reg<5>), reinterpret_cast<const void*>(&k_border_solve_reg<6>), reinterpret_cast<const void*>(&k_border_solve_reg<7>),
@@ -753,6 +762,7 @@ int set_func_attributes(hs_problem* p) {
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_backward2), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
 #endif
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_backward_sb), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_backward_pm), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_backward), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_border_solve), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   return HS_OK;

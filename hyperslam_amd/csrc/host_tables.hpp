@@ -297,6 +297,7 @@ struct hs_problem {
   int yt_stride = 0;
   bool wide_q = false;  // fused build on window-wide bands: landmark term once per window (k_landmark_gram_wide; HS_WIDE_Q=0: per chunk, round 5's arrangement)
   DBuf<double> d_Vb, d_Vb2, d_yt, d_yt2;  // block-row-scaled factors diag(U_jj^-1) U and right-hand sides for the register sweep
+  DBuf<double> d_Mb, d_Mb2;               // stacked blocks [Winv_J ; U[above, J] Winv_J] of the super-blocks of either end (k_band_backward_pm)
   DBuf<double> d_Sb2, d_g2, d_Ub2, d_Ubk2, d_ybuf2, d_win, d_xsol;  // two-ended factorisation: reversed system, its factor, junction window
   DBuf<unsigned> d_join;
   DBuf<double> d_dense_ut;     // k_dense_solve_mx: the factor by columns (256 x 256), read back by its sweep
@@ -785,6 +786,8 @@ int prepare(hs_problem* p) {
       p->zeroed_np = np, p->zeroed_ncb = ncb, std::memcpy(p->zeroed_ptr, now, sizeof(now));
     }
   }
+  if (6 * (vs.bw - 1) <= 96)  // (every entry a sweep reads is written by a builder of the same launch: nothing to zero)
+    for (DBuf<double>* b : {&p->d_Mb, &p->d_Mb2}) HIP_TRY(b->reserve(size_t((p->n_cp + kSb - 1) / kSb + 1) * sb_stack_doubles(vs.bw)));
   HIP_TRY(p->d_g2.reserve(np));
   HIP_TRY(p->d_Ub2.reserve(size_t(np) * ncb));
   HIP_TRY(p->d_Ubk2.reserve(size_t(p->n_cp) * 24));
@@ -895,7 +898,10 @@ int prepare(hs_problem* p) {
   T.fj[0] = FactorJob{T.Sb, T.g_s, T.Ub, T.Ubk, T.ybuf, nullptr, np / 6, -1};
   T.fj[1] = FactorJob{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, -1};
   T.xsol = p->d_xsol.p, T.join_flag = p->d_join.p, T.join_epoch = 0;
-  T.debug_flags = std::getenv("HS_DEBUG_FLAGS") ? std::atoi(std::getenv("HS_DEBUG_FLAGS")) : 0;
+  {  // (one number, 64 bits: the values of the first 32 switches are what atoi made of them)
+    const long long flags = std::getenv("HS_DEBUG_FLAGS") ? std::atoll(std::getenv("HS_DEBUG_FLAGS")) : 0;
+    T.debug_flags = int(flags), T.debug_flags2 = flags > 0 ? int(flags >> 32) : 0;
+  }
   {  // the reversed copy feeds the far end of a two-ended factorisation and, as the lower band, every MFMA factorisation
     const bool la_ok = la_compute_waves(vs.bw) > 0, two_ended = la_ok && np / 6 >= 4 * vs.bw;
     const bool need = two_ended || (HS_AB(T.debug_flags, 131072) && mfma_window_tiles(vs.bw) > 0);
@@ -927,6 +933,7 @@ int prepare(hs_problem* p) {
   // 8388608 five finalisation launches for a bordered single shard    16777216 k_commit launch for small windows    33554432 one cost launch per factor type
   // 134217728 prior / inertial candidate costs as launches of their own behind k_update_visual (single shard, fused path)
   // 16384 border gathers / pipelined border sweep joined to the main stream by events instead of device flags (Tables::gather_epoch, sweep_epoch)
+  // 4294967296 (debug_flags2 & 1, product A/B switch) backward sweep in two phases per super-step: k_band_backward_sb instead of k_band_backward_pm
   // 268435456 backward sweeps one block row per step    536870912 bordered systems one-ended    1073741824 no speculative linearisation at the candidate    67108864 k_commit in every iteration of a speculative solve
   T.st = p->d_state.p;
   HIP_TRY(p->batch.flush(s));  // (the staging arena outlives this call: no host synchronisation)

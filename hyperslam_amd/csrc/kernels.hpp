@@ -11,7 +11,8 @@
 //   k_band_factor_mx (two ends, bw <= 16: trailing window in f64-MFMA accumulators) | k_band_factor_la (one end; A/B) | k_band_factor
 //   (bw <= 22) | k_band_factor_wide (bw <= 42) | k_dense_factor                                                             S = U'U, y
 //   k_border_forward / _schur / _solve / _apply                                         bordered part of the solve
-//   k_band_backward | k_band_backward_sb     U x = y (two-ended: super-blocks of four block rows, inverses built by extra workgroups), step outputs
+//   k_band_backward | k_band_backward_pm     U x = y (bw <= 17: super-blocks of four block rows, one phase per step on the stacked blocks [Winv ; U Winv]
+//                                            built by extra workgroups; k_band_backward_sb: two phases per step, A/B), step outputs
 //   k_backsub_retract                        step for landmarks, candidate point = Plus(x, delta), norm / model-cost partials
 //   k_cost_visual / _prior / _inertial       cost at the candidate point
 //   k_pack_decision -> [all-reduce] -> k_decide -> k_commit      trust-region logic and acceptance

@@ -939,6 +939,7 @@ struct BackJob {
   int n_rows;   // block rows of this factor
   int given;    // block rows above them in sweep order whose solution comes from the other job
   int reversed; // solution index = np - 1 - rho
+  const double* Mb = nullptr;  // stacked blocks [Winv_J ; U[above, J] Winv_J] per super-block (k_band_backward_pm)
 };
 
 

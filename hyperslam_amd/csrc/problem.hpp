@@ -258,6 +258,7 @@ struct Tables {
                          // kernel's only output is x_b (+ the factorisation's verdict)
   int rank, world;
   int debug_flags;  // HS_DEBUG_FLAGS env (timing experiments; 0 in production)
+  int debug_flags2; // bits 32 .. of HS_DEBUG_FLAGS (every bit of debug_flags is taken)
   DevState* st;
 };
 

@@ -5,8 +5,8 @@ os.environ.setdefault("HS_STAGE_TIMING", "1")
 import hyperslam_amd as ha
 from hyperslam_amd import synthetic, _lib
 _lib.PRODUCT_LIB = os.path.join("tools", "libhyperslam_hip_prof.so")  # profiling build (tools/build_profiling_lib.sh): the product library has no timing hooks
-os.environ.setdefault("HS_DEBUG_FLAGS", "16")
-w=synthetic.config1()
+os.environ["HS_DEBUG_FLAGS"] = str(16 | int(os.environ.get("HS_DEBUG_FLAGS", "0")))
+w=getattr(synthetic, "config" + (sys.argv[1] if len(sys.argv) > 1 else "1"))()  # usage: python tools/chol_phase_timing.py [config=1]
 p=ha.Problem(w); p.snapshot()
 for i in range(2): p.restore(); s=p.solve(1)
 lib=_lib.load().cdll
@@ -38,11 +38,22 @@ for job in (0, 1):
           " junction reached", c[3] - b, " partner arrived", c[4] - b, " merged", c[5] - b, " X_m published", c[6] - b, " last row", c[7] - b,
           " window handed over", c[8] - b)
 
+# the backward sweep: k_band_backward_pm (one phase per super-step on premultiplied blocks) unless HS_DEBUG_FLAGS has 4294967296 (k_band_backward_sb);
+# both write the same stamps. Super-steps per block as launch_factor splits the system (block 1: + phase A, the near factor's top super-blocks).
+flags = int(os.environ["HS_DEBUG_FLAGS"])
+bw, n_blk = _lib.load().band_blocks(p.h), w.n_cp
+mx = 3 <= bw <= 16 and not flags & 64
+m = min((n_blk - (bw - 1)) // 2 + (2 if mx else 3), n_blk - 2 * (bw - 1)); mB = n_blk - (bw - 1) - m
+steps = [-(-(m + bw - 1) // 4), -(-mB // 4)]
+phase_a = steps[0] - m // 4
+print("backward sweep:", "k_band_backward_sb (two phases per super-step)" if flags & 4294967296 else "k_band_backward_pm (one phase per super-step)",
+      " bw", bw, " block rows near / far", m + bw - 1, mB, " super-steps", steps, " phase A steps of block 1", phase_a)
 for blk in (0, 1):
     c = buf[8 * (230 + 10 * blk): 8 * (230 + 10 * blk) + 8]
     b = buf[8 * 230]
-    print("backward block", blk, "[10 ns after block 0's start]: started", c[0] - b, " operands staged", c[1] - b, " middle arrived", c[2] - b, " sweep starts", c[3] - b,
-          " middle solved", c[4] - b, " published", c[5] - b, " sweep done", c[6] - b, " outputs", c[7] - b)
+    print("backward block", blk, "[10 ns after block 0's start]: started", c[0] - b, " operands staged / flags seen + requested", c[1] - b, " middle arrived / solved (phase A)", c[2] - b,
+          " sweep starts", c[3] - b, " middle solved", c[4] - b, " published", c[5] - b, " sweep done", c[6] - b, " outputs", c[7] - b,
+          " | per super-step [10 ns]: %.1f" % ((c[6] - c[3]) / steps[blk]))
 
 c = buf[8 * 260:8 * 260 + 4]; b = buf[8 * 230]
 print("builder of the last super-block of job 0 [10 ns after sweep block 0's start]: start", c[0] - b, " block in LDS", c[1] - b, " inverse done", c[2] - b, " flag raised", c[3] - b)
