@@ -220,7 +220,23 @@ inline void atomic_store(T* p, V value, int order) {
 }  // namespace hs_emul
 #define __hip_atomic_load(ptr, order, scope) hs_emul::atomic_load(ptr, order)
 #define __hip_atomic_store(ptr, value, order, scope) hs_emul::atomic_store(ptr, value, order)
-inline double __builtin_amdgcn_rsq(double d) { return 1.0 / std::sqrt(d); }
+/// v_rsq_f64 is an ESTIMATE on the hardware, and every pivot of the product is that estimate plus a hand-written correction: with an exact
+/// value here a missing or wrong correction changes nothing. So the emulated estimate is off by the relative error kRsqRelErr = 2^-23: the
+/// smallest power of two that is at least twice the hardware's worst error, 2^-24.22 on an MI355X (measured by tests/test_gpu_primitives.py,
+/// which asserts the hardware stays within half of kRsqRelErr):
+/// the correctly rounded value times 1 + kRsqRelErr where the lowest mantissa bit of d is set, 1 - kRsqRelErr where it is clear — a pure
+/// function of d's bits (the panels compute a pivot redundantly in several lanes and rely on equal results). Zeros, infinities and NaN (d = +-0,
+/// +inf, negative, NaN) pass through. tests/primitive_models.py reads the constant from this header.
+namespace hs_emul {
+constexpr double kRsqRelErr = 0x1p-23;
+}
+inline double __builtin_amdgcn_rsq(double d) {
+  const double y = 1.0 / std::sqrt(d);
+  if (!(y > 0.0) || !std::isfinite(y)) return y;
+  unsigned long long b;
+  std::memcpy(&b, &d, 8);
+  return y * ((b & 1ull) ? 1.0 + hs_emul::kRsqRelErr : 1.0 - hs_emul::kRsqRelErr);
+}
 inline double __builtin_amdgcn_rcp(double d) { return 1.0 / d; }
 inline long long wall_clock64() { return 0; }
 inline unsigned __builtin_amdgcn_s_getreg(int) { return 0; }

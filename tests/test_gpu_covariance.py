@@ -82,6 +82,8 @@ def bar(cond):
 
 
 def rel(a, b):
+    if np.size(a) == 0 or np.size(b) == 0:
+        raise ValueError(f"rel() of an empty selection (shapes {np.shape(a)} and {np.shape(b)}): nothing would be compared")
     return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
 
 
@@ -358,10 +360,17 @@ def test_wide_band_with_imu_border(hip, oracle):
 
 # ---- seeded sweep ---------------------------------------------------------------------------------------------------------------------------
 
+MAX_REPLACEMENTS = 32  # draws the referee may turn down for rank deficiency before 16 windows are found (a condition on the generator: decided
+                       # from CPU quantities before the device is consulted; tests/test_covariance_sweep_windows.py has the counts per seed)
+
+
 def sweep_windows(seed, oracle, n=16, max_draws=400):
-    """n windows of tools/fuzz_parity.py::cases(seed) of at most 64 control points and 120 landmarks, each with a frozen prefix of at least the
-    spline order (gauge) and without trailing bias control points no inertial row reaches. A window on which the referee itself finds rank
-    deficiency (cond not finite or above 1e12, or a singular block) is replaced by the next draw. Returns (windows, replacements)."""
+    """n windows of tools/fuzz_parity.py::cases(seed) of at most 64 control points and 120 landmarks, with at least one visual residual (a window
+    of priors / inertial rows alone has no landmark block for check_window to compare) and a band of at most 42 control points (the most the
+    library takes; the band restated on the CPU: calibration_windows.band_blocks), each with a frozen prefix of at least the spline order
+    (gauge) and without trailing bias control points no inertial row reaches. A window on which the referee itself finds rank deficiency (cond
+    not finite or above 1e12, or a singular block) is replaced by the next draw. Returns (windows, replacements)."""
+    from calibration_windows import MAX_BAND, band_blocks
     import os
     import sys
     tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
@@ -372,6 +381,8 @@ def sweep_windows(seed, oracle, n=16, max_draws=400):
     for tag, w in fuzz_parity.cases(max_draws, seed):
         if w.n_cp > 64 or len(w.landmarks) > 120:
             continue  # (the restriction of the generator, not a replacement)
+        if len(w.pixel_stamps) + len(w.bearing_stamps) == 0 or band_blocks(w) > MAX_BAND:
+            continue  # (restrictions of the generator as well)
         f0 = max(int(np.argmin(np.asarray(w.cp_constant, bool))), w.order)
         w.cp_constant = np.r_[np.ones(f0, np.uint8), np.zeros(w.n_cp - f0, np.uint8)]
         if w.imu is not None:
@@ -390,13 +401,14 @@ def sweep_windows(seed, oracle, n=16, max_draws=400):
 
 
 def test_random_windows(hip, oracle):
-    """16 random windows, seeded by the kernel sources (tests/test_gpu_fuzz.py::source_seed), through check_window. At most 16 replacements for
-    rank deficiency are allowed. On the CPU, seeds 1000 .. 1049 needed 0 .. 16 (mean 6), seeds 1 .. 200 the same but for seed 129, which needed 20:
-    the generator's windows with few landmarks on many control points fall apart into islands no gauge holds. Wall time on an MI355X box: 2 s."""
+    """16 random windows, seeded by the kernel sources (tests/test_gpu_fuzz.py::source_seed), through check_window. At most MAX_REPLACEMENTS = 32
+    replacements for rank deficiency are allowed: the generator's windows with few landmarks on many control points fall apart into islands no
+    gauge holds; over seeds 1 .. 300 and 1000 .. 1059 the generator needed 0 .. 16 (mean 5.3; tests/test_covariance_sweep_windows.py, which also
+    has the seeds whose windows sweep_windows has to leave out as restrictions of the generator). Wall time on an MI355X box: 2 s."""
     from test_gpu_fuzz import source_seed
     seed = source_seed()
     windows, replaced = sweep_windows(seed, oracle)
-    assert len(windows) == 16 and replaced <= 16, f"seed {seed}: {len(windows)} windows, {replaced} replacements"
+    assert len(windows) == 16 and replaced <= MAX_REPLACEMENTS, f"seed {seed}: {len(windows)} windows, {replaced} replacements"
     for tag, w in windows:
         try:
             check_window(w, hip, oracle)
