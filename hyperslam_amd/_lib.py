@@ -145,9 +145,11 @@ _PRODUCT_ONLY = {
     # free camera blocks (the oracle keeps every sensor block constant)
     "set_camera_constancy": (C.c_int, [C.c_void_p, C.c_int, c_uint8_p]),
     "set_camera_estimation": (C.c_int, [C.c_void_p, C.c_int]),
+    "set_camera_covariance": (C.c_int, [C.c_void_p, C.c_int]),
     "get_cameras": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
     "compute_covariance": (C.c_int, [C.c_void_p]),
     "get_covariance": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "get_covariance_cross": (C.c_int, [C.c_void_p, c_double_p]),
     "sample_covariance": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
     # stereo KLT front-end (hs_tracker handle; the oracle has no counterpart)
     "tracker_default_options": (C.c_int, [C.c_void_p]),

@@ -191,6 +191,16 @@ int hs_set_camera_estimation(hs_problem* p, int enabled) {
   return HS_OK;
 }
 
+/// hs_compute_covariance takes the free camera blocks of this handle (off by default: it refuses them).
+int hs_set_camera_covariance(hs_problem* p, int enabled) {
+  if (!p) return HS_ERR_INVALID;
+  const bool on = enabled != 0;
+  if (on == p->cam_covariance) return HS_OK;
+  p->cam_covariance = on;
+  if (camera_columns(p, nullptr)) p->cov_valid = false;  // (no table depends on it: the build is hs_reduced_system's either way)
+  return HS_OK;
+}
+
 int hs_get_cameras(hs_problem* p, double* T_bs, double* intr, double* dist) {
   if (!p) return HS_ERR_INVALID;
   for (int i = 0; i < p->n_cam; ++i) {
@@ -773,7 +783,8 @@ int hs_compute_covariance(hs_problem* p) {
   if (!p) return HS_ERR_INVALID;
   if (p->has_weights()) HS_FAIL(HS_ERR_INVALID, kWeightsMessage);
   if (p->world > 1) HS_FAIL(HS_ERR_STATE, "hs_compute_covariance: sharded handles (world > 1) are not supported");
-  if (camera_columns(p, nullptr)) HS_FAIL(HS_ERR_STATE, "hs_compute_covariance: free camera blocks (hs_set_camera_constancy) are not supported");
+  if (!p->cam_covariance && camera_columns(p, nullptr))  // (taking them is opt-in per handle: hs_set_camera_covariance)
+    HS_FAIL(HS_ERR_STATE, "hs_compute_covariance: free camera blocks (hs_set_camera_constancy) are not supported");
   p->cov_valid = false;
   int rc = prepare(p);
   if (rc) return rc;
@@ -786,9 +797,10 @@ int hs_compute_covariance(hs_problem* p) {
   const Tables& T = p->T;
   const int np = T.np, ncb = 6 * T.bw, nb = T.nb, n_lm = T.n_lm;
   if (T.bw < p->k) HS_FAIL(HS_ERR_NUMERIC, "hs_compute_covariance: no residual couples the control points of one spline segment");
-  std::vector<uint8_t> cc(size_t(np) + nb);  // constant coordinates: control points (whole or rotation / translation), bias splines, gravity
+  const int nbi = nb - T.nc;  // bias splines + gravity; the camera columns behind them are free coordinates (camera_columns)
+  std::vector<uint8_t> cc(size_t(np) + nb, 0);  // constant coordinates: control points (whole or rotation / translation), bias splines, gravity
   for (int r = 0; r < np; ++r) cc[r] = p->cp_const[r / 6] || (r % 6 < 3 ? p->rot_const : p->trans_const);
-  for (int b = 0; b < nb; ++b) cc[np + b] = b < 6 * p->n_bias ? p->bias_const != 0 : p->gravity_const != 0;
+  for (int b = 0; b < nbi; ++b) cc[np + b] = b < 6 * p->n_bias ? p->bias_const != 0 : p->gravity_const != 0;
   hipStream_t s = p->stream;
   const size_t nband = size_t(np) * ncb, npb = size_t(np) * nb + 1, nbb = size_t(nb) * nb + 1;
   HIP_TRY(p->d_cov_const.upload(cc, s));
@@ -815,7 +827,11 @@ int hs_compute_covariance(hs_problem* p) {
     k_cov_band<false><<<1, kBlock, cov_band_lds_doubles(false, ncb) * sizeof(double), s>>>(B);
   }
   k_cov_finish<<<T.sp.n_cp, kBlock, size_t(6) * nb * sizeof(double), s>>>(B);
-  if (n_lm) k_cov_landmarks<<<(n_lm + kBlock / 64 - 1) / (kBlock / 64), kBlock, 0, s>>>(T, p->d_cov_band.p, p->d_cov_lm.p, p->d_cov_lm_status.p);
+  if (n_lm && T.nc)  // (the cameras move with the landmarks: Sigma_pb and Sigma_bb enter the landmark blocks)
+    k_cov_landmarks_cam<<<(n_lm + kBlock / 64 - 1) / (kBlock / 64), kBlock, cov_landmarks_cam_lds_doubles(T.bw, T.nc) * sizeof(double), s>>>(
+        T, p->d_cov_band.p, p->d_cov_pb.p, p->d_cov_bb.p, p->d_cov_lm.p, p->d_cov_lm_status.p);
+  else if (n_lm)
+    k_cov_landmarks<<<(n_lm + kBlock / 64 - 1) / (kBlock / 64), kBlock, 0, s>>>(T, p->d_cov_band.p, p->d_cov_lm.p, p->d_cov_lm_status.p);
   HIP_TRY(hipGetLastError());
   int status = 0;
   std::vector<int> lm_status(n_lm);
@@ -829,6 +845,13 @@ int hs_compute_covariance(hs_problem* p) {
     if (c < np)
       HS_FAIL(HS_ERR_NUMERIC, "hs_compute_covariance: rank deficient at control point " + std::to_string(c / 6) + " (local coordinate " +
                                   std::to_string(c % 6) + "): a free coordinate without information (gauge not fixed, or no residual touches it)");
+    if (c - np >= nbi) {
+      static const char* const block[3] = {"T_bs", "intrinsics", "distortion"};
+      const int m = p->calib_map[c - np - nbi], col = m & 0xff, b = col < 6 ? 0 : (col < 10 ? 1 : 2);
+      HS_FAIL(HS_ERR_NUMERIC, "hs_compute_covariance: rank deficient at border unknown " + std::to_string(c - np) + " (camera " + std::to_string(m >> 8) +
+                                  ", " + block[b] + " coordinate " + std::to_string(col - (b == 0 ? 0 : (b == 1 ? 6 : 10))) +
+                                  "): a free camera coordinate without information (no residual of the window depends on it, or the window does not fix it)");
+    }
     HS_FAIL(HS_ERR_NUMERIC, "hs_compute_covariance: rank deficient at border unknown " + std::to_string(c - np) + " (" +
                                 (c - np < 6 * p->n_bias ? "bias control point " + std::to_string((c - np) % (3 * p->n_bias) / 3) : std::string("gravity")) + ")");
   }
@@ -867,6 +890,15 @@ int hs_get_covariance(hs_problem* p, double* cp_blocks, double* cp_band, double*
         }
   if (landmarks)
     for (int d = 0; d < n_lm; ++d) std::memcpy(landmarks + size_t(9) * p->vs.table_of_dev[d], lm.data() + size_t(9) * d, 9 * sizeof(double));
+  return HS_OK;
+}
+
+int hs_get_covariance_cross(hs_problem* p, double* cp_border) {
+  if (!p || !cp_border) return HS_ERR_INVALID;
+  if (!p->cov_valid) HS_FAIL(HS_ERR_STATE, "hs_get_covariance_cross: no covariance of the current state (call hs_compute_covariance after the last change)");
+  if (p->cov_nb == 0) return HS_OK;
+  HIP_TRY(hipMemcpyAsync(cp_border, p->d_cov_pb.p, size_t(p->cov_np) * p->cov_nb * 8, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
   return HS_OK;
 }
 

@@ -233,6 +233,7 @@ struct hs_problem {
   std::vector<double> cam;  // n x 16
   std::vector<uint8_t> cam_const;  // hs_set_camera_constancy: n x 3 [T_bs, intrinsics, distortion]; empty: every block constant (camera.hpp:18)
   bool cam_estimation = false;     // hs_set_camera_estimation: hs_solve estimates the free blocks (off: it refuses a handle that has one)
+  bool cam_covariance = false;     // hs_set_camera_covariance: hs_compute_covariance takes the free blocks (off: it refuses a handle that has one)
   std::vector<double> cam_snap;    // hs_snapshot: the camera table (host copy; hs_solve keeps `cam` equal to the device table)
   int n_sensor = 0;
   std::vector<double> sensor;  // n x 8

@@ -12,6 +12,8 @@
 //                                     every operand lies in the band rows of the block-aligned layout, so the recurrence closes on it.
 //   k_cov_finish     (block rows)     Sig_pp = Sig + X C X', Sig_pb = -X C, Sig_bb = C, unscaled: Sigma = D Sig D
 //   k_cov_landmarks  (wave/landmark)  Sigma_ll = S_l L^-T (I + Yh' Sigma_pp Yh) L^-1 S_l from the <= bw band blocks the landmark touches
+//   k_cov_landmarks_cam (wave/landmark)  the same with free camera coordinates in the border (hs_set_camera_covariance): G = [Yh ; Y_c'] over
+//                                     the landmark's pose rows and the camera columns, Sigma from the band, Sigma_pb and Sigma_bb
 //   k_cov_sample     (wave/stamp)     J(t) Sigma_cp J(t)', J(t) = the state Jacobian of the pose prior with its measurement at the pose at t
 // Constant coordinates are decoupled rows (identity in the factor, zero covariance); a free coordinate whose pivot is not positive or falls
 // below kCovPivotTol of its scaled diagonal — the build's marker 1.0 of a structurally zero column included — ends the factorisation and
@@ -313,6 +315,97 @@ __global__ void __launch_bounds__(kBlock) k_cov_landmarks(Tables T, const double
   for (int a = 0; a < 3; ++a)
 #pragma unroll
     for (int b = 0; b < 3; ++b) AN[3 * a + b] = A[3 * a] * N[b] + A[3 * a + 1] * N[3 + b] + A[3 * a + 2] * N[6 + b];
+  const double* sl = T.lm_scale + 3 * size_t(dl);
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const double v = N[a] * AN[b] + N[3 + a] * AN[3 + b] + N[6 + a] * AN[6 + b];  // (N' A N)(a, b)
+      out[9 * size_t(dl) + 3 * a + b] = ok ? sl[a] * v * sl[b] : __builtin_nan("");
+    }
+}
+
+/// Dynamic LDS of k_cov_landmarks_cam, in doubles: per wave the rows of G of the widest landmark (6 bw pose rows) and the nc camera rows.
+inline size_t cov_landmarks_cam_lds_doubles(int bw, int nc) { return size_t(kBlock / 64) * 3 * (6 * bw + nc); }
+
+/// Handles with free camera coordinates (T.nc > 0, the last nc border columns; kernels_calib.hpp). One wave per device landmark. The camera
+/// moves with the landmark, delta_l = -S_l L^-T (yh - Yh' delta_p - Y_c delta_c), so with G = [Yh ; Y_c'] over [p_l ; c] — the
+/// 6 n_l pose rows the landmark touches, then the nc camera coordinates —
+///   Sigma_ll = S_l L^-T (I + G' Sigma_[p_l,c] G) L^-1 S_l,
+/// Sigma_[p_l,c] read in place from the band (cov), the camera columns of Sigma_pb (cov_pb) and the trailing nc x nc block of Sigma_bb
+/// (cov_bb), all unscaled. A lane owns the rows r = lane, lane + 64, ... of Sigma G (up to 6 * 42 + 64 = 316 rows); G is staged in the wave's
+/// slice of dynamic LDS (cov_landmarks_cam_lds_doubles). Constant / unobserved landmarks and the rank test: as in k_cov_landmarks, which
+/// handles without free camera coordinates keep launching. Fixed order in every sum: two computations are bit-identical.
+__global__ void __launch_bounds__(kBlock) k_cov_landmarks_cam(Tables T, const double* cov, const double* cov_pb, const double* cov_bb, double* out, int* status) {
+  HS_DYNAMIC_LDS(smem);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, dl = blockIdx.x * (kBlock / 64) + w;
+  if (dl >= T.n_lm) return;
+  const int ncb = 6 * T.bw, nc = T.nc, nb = T.nb, nbi = T.nb - T.nc;
+  const bool observed = T.lm_ptr[dl + 1] > T.lm_ptr[dl];
+  if (!observed || T.lm_const[dl]) {
+    if (lane < 9) out[9 * size_t(dl) + lane] = observed ? 0.0 : __builtin_nan("");
+    if (lane == 0) status[dl] = 0;
+    return;
+  }
+  const int rows = 6 * T.lm_ncp[dl], r0 = 6 * T.lm_cfirst[dl], nr = rows + nc;
+  const double* Y = T.Y + T.lm_yoff[dl];
+  const double* Yc = T.calib_Yc + size_t(dl) * 3 * nc;  // 3 x nc
+  double* G = smem + size_t(w) * 3 * (ncb + nc);         // nr x 3
+  for (int e = lane; e < 3 * rows; e += 64) G[e] = Y[e];
+  for (int e = lane; e < 3 * nc; e += 64) G[3 * (rows + e % nc) + e / nc] = Yc[e];
+  wait_lds();  // (hand-over between the lanes of one wave)
+  double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int r = lane; r < nr; r += 64) {
+    double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+    const double* Gc = G + 3 * rows;
+    if (r < rows) {  // a pose row: [band | camera columns of Sigma_pb]
+      for (int c = 0; c < rows; ++c) {
+        const double s = cov_band_at(cov, ncb, r0 + r, r0 + c);
+        t0 = fma(s, G[3 * c], t0), t1 = fma(s, G[3 * c + 1], t1), t2 = fma(s, G[3 * c + 2], t2);
+      }
+      const double* pb = cov_pb + size_t(r0 + r) * nb + nbi;
+      for (int c = 0; c < nc; ++c) {
+        const double s = pb[c];
+        t0 = fma(s, Gc[3 * c], t0), t1 = fma(s, Gc[3 * c + 1], t1), t2 = fma(s, Gc[3 * c + 2], t2);
+      }
+    } else {  // a camera row: [camera column of Sigma_pb, transposed | trailing block of Sigma_bb]
+      const int a = nbi + (r - rows);
+      for (int c = 0; c < rows; ++c) {
+        const double s = cov_pb[size_t(r0 + c) * nb + a];
+        t0 = fma(s, G[3 * c], t0), t1 = fma(s, G[3 * c + 1], t1), t2 = fma(s, G[3 * c + 2], t2);
+      }
+      const double* bb = cov_bb + size_t(a) * nb + nbi;
+      for (int c = 0; c < nc; ++c) {
+        const double s = bb[c];
+        t0 = fma(s, Gc[3 * c], t0), t1 = fma(s, Gc[3 * c + 1], t1), t2 = fma(s, Gc[3 * c + 2], t2);
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double y = G[3 * r + a];
+      m[3 * a] = fma(y, t0, m[3 * a]), m[3 * a + 1] = fma(y, t1, m[3 * a + 1]), m[3 * a + 2] = fma(y, t2, m[3 * a + 2]);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 9; ++e) m[e] = wave_sum(m[e]);
+  if (lane != 0) return;
+  // (from here on the tail of k_cov_landmarks, restated: that kernel is left exactly as it is)
+  const double* Lf = T.lm_L + 6 * size_t(dl);
+  const double l00 = Lf[0], l10 = Lf[1], l11 = Lf[2], l20 = Lf[3], l21 = Lf[4], l22 = Lf[5];
+  const bool ok = l00 > 0.0 && l11 > 0.0 && l22 > 0.0 && l11 * l11 > kCovPivotTol * (l10 * l10 + l11 * l11) &&
+                  l22 * l22 > kCovPivotTol * (l20 * l20 + l21 * l21 + l22 * l22) && isfinite(l00 + l10 + l11 + l20 + l21 + l22);
+  status[dl] = ok ? 0 : 1;
+  const double n00 = 1.0 / l00, n11 = 1.0 / l11, n22 = 1.0 / l22;
+  const double n10 = -l10 * n00 * n11, n21 = -l21 * n11 * n22, n20 = -(l20 * n00 + l21 * n10) * n22;
+  const double N[9] = {n00, 0.0, 0.0, n10, n11, 0.0, n20, n21, n22};  // N = L^-1 (lower)
+  double AN[9];  // (I + G' Sigma G) N
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const double a0 = m[3 * a] + (a == 0 ? 1.0 : 0.0), a1 = m[3 * a + 1] + (a == 1 ? 1.0 : 0.0), a2 = m[3 * a + 2] + (a == 2 ? 1.0 : 0.0);
+      AN[3 * a + b] = a0 * N[b] + a1 * N[3 + b] + a2 * N[6 + b];
+    }
   const double* sl = T.lm_scale + 3 * size_t(dl);
 #pragma unroll
   for (int a = 0; a < 3; ++a)

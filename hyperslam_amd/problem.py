@@ -328,13 +328,16 @@ class Problem:
 
     def covariance(self):
         """What compute_covariance() computed, in Ceres-local coordinates: control_points (n_cp, 6, 6), control_point_band (n_cp, bw, 6, 6) —
-        entry [i, j] is the block of control points (i, i + j) —, landmarks (n_lm, 3, 3) in table order, border (nb, nb) (bias splines, gravity)."""
+        entry [i, j] is the block of control points (i, i + j) —, landmarks (n_lm, 3, 3) in table order, border (nb, nb) (bias splines, gravity,
+        then the free camera coordinates of set_camera_covariance, in the column order of reduced_system) and control_point_border
+        (n_cp, 6, nb), the covariance between each control point and the border unknowns."""
         n_cp, bw = self.window.n_cp, self.lib.band_blocks(self.h)
         n_lm, nb = self.num_landmarks(), self.dim_pose() - 6 * n_cp
         cpb, band = np.zeros((n_cp, 6, 6)), np.zeros((n_cp, bw, 6, 6))
-        lm, border = np.zeros((n_lm, 3, 3)), np.zeros((nb, nb))
+        lm, border, cross = np.zeros((n_lm, 3, 3)), np.zeros((nb, nb)), np.zeros((n_cp, 6, nb))
         self._check(self.lib.get_covariance(self.h, _d(cpb), _d(band), _d(lm), _d(border)), "get_covariance")
-        return dict(control_points=cpb, control_point_band=band, landmarks=lm, border=border)
+        self._check(self.lib.get_covariance_cross(self.h, _d(cross)), "get_covariance_cross")
+        return dict(control_points=cpb, control_point_band=band, landmarks=lm, border=border, control_point_border=cross)
 
     def sample_covariance(self, stamps):
         """Covariance (n, 6, 6) of the pose at each stamp, in the residual coordinates of the pose prior [rotation ; position]."""
@@ -370,6 +373,12 @@ class Problem:
         if not hasattr(self.lib, "set_camera_estimation"):
             raise HsError(f"{self.lib.prefix}set_camera_estimation: not provided by this library (sensor blocks are constant there)")
         self._check(self.lib.set_camera_estimation(self.h, int(bool(enabled))), "set_camera_estimation")
+
+    def set_camera_covariance(self, enabled=True):
+        """compute_covariance() takes the free camera blocks of set_camera_constancy on this handle (off by default: it refuses them)."""
+        if not hasattr(self.lib, "set_camera_covariance"):
+            raise HsError(f"{self.lib.prefix}set_camera_covariance: not provided by this library (sensor blocks are constant there)")
+        self._check(self.lib.set_camera_covariance(self.h, int(bool(enabled))), "set_camera_covariance")
 
     def cameras(self):
         """Current camera values (T_bs (n, 7), intrinsics (n, 4), distortion (n, 4)) in the layout of the window's tables."""

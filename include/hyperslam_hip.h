@@ -137,7 +137,8 @@ int hs_set_cameras(hs_problem* p, int n, const double* T_bs, const double* intri
  * T_bs only (their intrinsics / distortion columns are zero). A camera no visual residual references is left out. At most 64 free camera
  * coordinates per window (HS_ERR_INVALID from the call that prepares the tables). hs_solve estimates the free blocks once
  * hs_set_camera_estimation has enabled it on the handle; by default it refuses a handle with free camera coordinates (HS_ERR_STATE).
- * hs_compute_covariance refuses such a handle (HS_ERR_STATE), and so do hs_solve and hs_reduced_system on a sharded one (world > 1). */
+ * hs_compute_covariance takes them once hs_set_camera_covariance has enabled it on the handle; by default it refuses such a handle
+ * (HS_ERR_STATE). hs_solve and hs_reduced_system refuse a sharded handle (world > 1) with free camera coordinates. */
 int hs_set_camera_constancy(hs_problem* p, int n, const uint8_t* constant);
 /* hs_solve estimates the free camera blocks of hs_set_camera_constancy on this handle (enabled != 0). Off by default: hs_solve then refuses
  * a handle with free camera coordinates exactly as before (HS_ERR_STATE). An accepted step moves the camera table like every other variable:
@@ -146,6 +147,13 @@ int hs_set_camera_constancy(hs_problem* p, int n, const uint8_t* constant);
  * (bias / gravity + camera coordinates) is limited to 137 unknowns and the window to 400 control points (HS_ERR_INVALID from the call that
  * prepares the tables, naming the limit). Handles without a free camera coordinate are not affected by the switch. DESIGN.md section 13. */
 int hs_set_camera_estimation(hs_problem* p, int enabled);
+/* hs_compute_covariance takes the free camera blocks of hs_set_camera_constancy on this handle (enabled != 0): their coordinates are free
+ * border unknowns of the covariance, in the column order of hs_reduced_system, and the landmark blocks account for the cameras moving with
+ * the landmarks. Off by default: hs_compute_covariance then refuses a handle with free camera coordinates exactly as before (HS_ERR_STATE).
+ * Independent of hs_set_camera_estimation, whose limits (137 border unknowns, 400 control points) do not apply: the only limit is the 64
+ * free camera coordinates of hs_set_camera_constancy. Toggling it makes a computed covariance stale. Handles without a free camera
+ * coordinate are not affected by the switch. DESIGN.md section 12. */
+int hs_set_camera_covariance(hs_problem* p, int enabled);
 /* Current camera values in the layout of hs_set_cameras (n x 7, n x 4, n x 4). Each pointer may be NULL. */
 int hs_get_cameras(hs_problem* p, double* T_bs, double* intrinsics, double* distortion);
 /* Plain sensors (extrinsics only) used by pose-prior factors (manifold.cpp:30-33). T_bs n x 7. */
@@ -243,8 +251,12 @@ int hs_reduced_system(hs_problem* p, double radius, double* S, double* g);
 /* The covariance is the inverse of the undamped Gauss-Newton matrix J'J at the values the device holds (what hs_get_* return), built as the
  * solver builds it: robustified Jacobians (Ceres' loss corrector), landmarks eliminated by Schur complement, zero LM damping. Coordinates are
  * Ceres-local, the columns of hs_linearize: control points [d_rot(3) d_trans(3)], landmarks Euclidean (3), bias control points R3 each,
- * gravity the 2-dim SphereManifold basis; the border unknowns in the column order of hs_reduced_system (bias_g points, bias_a points, gravity).
- * Constant control points / landmarks / bias splines / gravity have zero covariance (as in Ceres); sensor blocks are constant, as in the solver.
+ * gravity the 2-dim SphereManifold basis, free camera blocks as in hs_set_camera_constancy; the border unknowns in the column order of
+ * hs_reduced_system (bias_g points, bias_a points, gravity, free camera coordinates).
+ * Constant control points / landmarks / bias splines / gravity have zero covariance (as in Ceres). Camera blocks are constant unless
+ * hs_set_camera_constancy frees them AND hs_set_camera_covariance is on; a handle with free camera coordinates and the switch off is refused
+ * (HS_ERR_STATE). A free camera coordinate without information (the intrinsics of a camera seen through bearing rows only, say) gives
+ * HS_ERR_NUMERIC naming "camera <c>, <T_bs|intrinsics|distortion> coordinate <j>".
  * A free coordinate without information (a structurally zero column, a non-positive pivot, or a pivot below 1e-12 of its Jacobi-scaled diagonal;
  * per landmark: of its scaled 3x3 block) gives HS_ERR_NUMERIC with a message naming the control point, border unknown or landmark.
  * Fixing the gauge is the caller's business: an almost singular gauge direction is not guaranteed to be caught.
@@ -253,8 +265,12 @@ int hs_reduced_system(hs_problem* p, double radius, double* S, double* g);
 int hs_compute_covariance(hs_problem* p);
 /* cp_blocks n_cp x 6 x 6 (marginals); cp_band n_cp x bw x 6 x 6, entry (i, j) = block (i, i + j) (zero past the last control point,
  * bw = hs_band_blocks); landmarks n_lm x 3 x 3 (table order; NaN for a landmark without residual rows: it is not in the problem);
- * border nb x nb, nb = hs_dim_pose - 6 n_cp. Each pointer is nullable. */
+ * border nb x nb, nb = hs_dim_pose - 6 n_cp: bias_g points, bias_a points, gravity, then the free camera coordinates (with
+ * hs_set_camera_covariance) in the column order of hs_reduced_system. Each pointer is nullable. */
 int hs_get_covariance(hs_problem* p, double* cp_blocks, double* cp_band, double* landmarks, double* border);
+/* cp_border 6 n_cp x nb, row-major: the covariance between the control-point coordinates (rows) and the border unknowns (columns, as in
+ * hs_get_covariance). Rows of constant control points and columns of constant border unknowns are zero. HS_ERR_STATE when stale. */
+int hs_get_covariance_cross(hs_problem* p, double* cp_border);
 /* Covariance of the pose at n stamps (n x 6 x 6, the residual coordinates of HS_PRIOR: [Log(R_m' R) ; p - p_m] with the measurement at the
  * pose itself): J(t) Sigma J(t)' over the k control points the pose depends on. HS_ERR_INVALID for a stamp outside the valid range. */
 int hs_sample_covariance(hs_problem* p, int n, const double* stamps, double* cov);
