@@ -256,6 +256,26 @@ int hs_set_imu(hs_problem* p, const double* T_bs, const double* i_g, const doubl
   return HS_OK;
 }
 
+static const char* kImuShardMessage = "free IMU blocks (hs_set_imu_constancy) are not supported on sharded handles (world > 1)";
+
+/// Manifold<Sensor>::setTransformationConstant, Manifold<IMU>::setGyroscopeIntrinsicsConstant / setAccelerometerIntrinsicsConstant and the
+/// S_g / X_a blocks the inertial evaluator fills next to them (sensor.cpp:26-29, inertial.cpp:155-194). The flags belong to the handle:
+/// hs_set_imu keeps them.
+int hs_set_imu_constancy(hs_problem* p, const uint8_t* constant) {
+  if (!p) return HS_ERR_INVALID;
+  std::vector<uint8_t> flags;
+  if (constant) {
+    flags.resize(5);
+    bool any_free = false;
+    for (size_t i = 0; i < flags.size(); ++i) flags[i] = constant[i] ? 1 : 0, any_free |= !flags[i];
+    if (!any_free) flags.clear();  // (every block constant: the default, and the same tables)
+  }
+  if (flags == p->imu_const) return HS_OK;
+  p->imu_const.swap(flags);
+  p->touch(hs_problem::kTail);  // (border layout and sizes)
+  return HS_OK;
+}
+
 int hs_set_inertial_jacobian(hs_problem* p, int mode) {
   if (!p) return HS_ERR_INVALID;
   if (mode != HS_INERTIAL_AS_REFERENCE && mode != HS_INERTIAL_EXACT) HS_FAIL(HS_ERR_INVALID, "unknown inertial Jacobian mode");
@@ -446,7 +466,7 @@ int hs_num_residuals(hs_problem* p, int type) {
   }
   return -1;
 }
-int hs_dim_pose(hs_problem* p) { return p ? 6 * p->n_cp + (p->has_imu ? 6 * p->n_bias + 2 : 0) + camera_columns(p, nullptr) : -1; }
+int hs_dim_pose(hs_problem* p) { return p ? 6 * p->n_cp + (p->has_imu ? 6 * p->n_bias + 2 : 0) + imu_columns(p, nullptr) + camera_columns(p, nullptr) : -1; }
 
 int hs_residual_layout(hs_problem* p, int type, int idx, int32_t* num_blocks, int32_t* indices, int32_t* sizes, int32_t* offsets, int32_t* block_ids,
                        int32_t* num_parameters, int32_t* num_residuals) {
@@ -733,6 +753,7 @@ int hs_reduced_system(hs_problem* p, double radius, double* S, double* g) {
   if (!p || !S || !g) return HS_ERR_INVALID;
   if (p->has_weights()) HS_FAIL(HS_ERR_INVALID, kWeightsMessage);
   if (p->world > 1 && camera_columns(p, nullptr)) HS_FAIL(HS_ERR_STATE, kCameraShardMessage);
+  if (p->world > 1 && imu_columns(p, nullptr)) HS_FAIL(HS_ERR_STATE, kImuShardMessage);
   int rc = prepare(p);
   if (rc) return rc;
   rc = reset_state(p, 1, radius);
@@ -783,6 +804,9 @@ int hs_compute_covariance(hs_problem* p) {
   if (!p) return HS_ERR_INVALID;
   if (p->has_weights()) HS_FAIL(HS_ERR_INVALID, kWeightsMessage);
   if (p->world > 1) HS_FAIL(HS_ERR_STATE, "hs_compute_covariance: sharded handles (world > 1) are not supported");
+  if (imu_columns(p, nullptr))  // (whatever hs_set_camera_covariance says)
+    HS_FAIL(HS_ERR_STATE, "hs_compute_covariance: free IMU blocks (hs_set_imu_constancy) are not supported; hs_reduced_system builds their system "
+                          "(DESIGN.md section 14)");
   if (!p->cam_covariance && camera_columns(p, nullptr))  // (taking them is opt-in per handle: hs_set_camera_covariance)
     HS_FAIL(HS_ERR_STATE, "hs_compute_covariance: free camera blocks (hs_set_camera_constancy) are not supported");
   p->cov_valid = false;
@@ -950,6 +974,11 @@ int hs_solve(hs_problem* p, int max_iterations, hs_summary* summary, hs_iteratio
   if (!p || !summary) return HS_ERR_INVALID;
   if (p->has_weights()) HS_FAIL(HS_ERR_INVALID, kWeightsMessage);
   if (max_iterations < 0 || max_iterations > kMaxIterations) HS_FAIL(HS_ERR_INVALID, "max_iterations out of range");
+  if (imu_columns(p, nullptr)) {  // (whatever hs_set_camera_estimation says)
+    if (p->world > 1) HS_FAIL(HS_ERR_STATE, kImuShardMessage);
+    HS_FAIL(HS_ERR_STATE, "hs_solve: free IMU blocks (hs_set_imu_constancy) are not supported by the solver in this version; "
+                          "hs_reduced_system builds their system (DESIGN.md section 14)");
+  }
   if (camera_columns(p, nullptr)) {
     if (p->world > 1) HS_FAIL(HS_ERR_STATE, kCameraShardMessage);
     if (!p->cam_estimation)  // (estimating them is opt-in per handle: hs_set_camera_estimation)

@@ -46,7 +46,7 @@ template <int K>
 int launch_linearize(hs_problem* p, bool inertial_on_side = false, bool visual_cost_only = false) {
   const Tables& T = p->T;
   hipStream_t s = p->stream;
-  p->side_imu = inertial_on_side && T.n_ine > 0 && T.nb > 0 && !T.nc && !(T.debug_flags & 1048576);  // A/B switch 1048576: one stream
+  p->side_imu = inertial_on_side && T.n_ine > 0 && T.nb > 0 && !T.nc && !p->ni && !(T.debug_flags & 1048576);  // A/B switch 1048576: one stream
   if (p->side_imu) {
     const int rc = ensure_side_stream(p);
     if (rc) return rc;
@@ -260,6 +260,16 @@ int launch_build(hs_problem* p, hipEvent_t after_build = nullptr, bool scaling_f
   if (T.nb > T.nc && !side_imu) {  // (bias / gravity columns: with an IMU only — free camera columns alone are not gathered here)
     k_border_pb<K><<<dim3(T.sp.n_cp + border_zero_wgs(T), p->n_split), kPbThreads, 0, s>>>(T);
     k_border_bb<K><<<T.n_bias, kBlock, 0, s>>>(T);
+  }
+  if (p->ni) {  // free IMU coordinates (kernels_imucal.hpp): behind the zero fill of k_border_pb and k_border_bb, on the main stream (side_imu is off)
+    constexpr int E = kImuCalGroup * kImuCalGroup;
+    const int n_groups = imucal_groups(p->ni), n_jobs = imucal_jobs(p->ni), n_chunks = (T.n_ine + kImuCalChunk - 1) / kImuCalChunk;
+    const ImuCal A{p->d_imucal_rec.p, p->d_imucal_map.p, p->d_imucal_part.p, p->d_imucal_part.p + size_t(n_chunks) * n_jobs * E, p->ni, 6 * T.n_bias + 2};
+    k_imucal_rows<K><<<(T.n_ine + kBlock - 1) / kBlock, kBlock, 0, s>>>(T, A);
+    k_imucal_pi<K><<<dim3(T.sp.n_cp, n_groups), kBlock, 0, s>>>(T, A, p->n_split);
+    k_imucal_bb<K><<<dim3(T.n_bias, n_groups, imucal_slices(T.n_ine)), kBlock, 0, s>>>(T, A);
+    k_imucal_ii<K><<<dim3(n_chunks, n_jobs), kBlock, 0, s>>>(T, A);
+    k_imucal_finish<<<((n_jobs + T.n_bias * n_groups) * E + kBlock - 1) / kBlock, kBlock, 0, s>>>(T, A, n_chunks, imucal_slices(T.n_ine));
   }
   if (T.nc) {  // free camera coordinates (kernels_calib.hpp): behind the landmark factors and the IMU gathers, on the main stream
     const int n_row_chunks = (T.n_vis + kCalibRowChunk - 1) / kCalibRowChunk, n_parts = n_row_chunks + (T.n_lm + kCalibLmChunk - 1) / kCalibLmChunk;

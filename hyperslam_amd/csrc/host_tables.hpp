@@ -251,6 +251,7 @@ struct hs_problem {
   double gravity[3] = {0, 0, -9.80665};
   int gravity_const = 1;
   int inertial_mode = HS_INERTIAL_AS_REFERENCE;  // hs_set_inertial_jacobian
+  std::vector<uint8_t> imu_const;                // hs_set_imu_constancy: [T_bs, i_g, i_a, S_g, X_a]; empty: every block constant (imu.hpp:18)
   hs_problem* scratch = nullptr;                 // one-residual handle of hs_cost_function_evaluate (created on first use)
   int frozen_prefix = 0;                         // leading constant control points: decoupled block rows of the reduced system
   bool stage_timing = false;                     // hs_set_stage_timing
@@ -334,6 +335,11 @@ struct hs_problem {
   DBuf<int> d_calib_map;
   DBuf<double> d_calib_rec, d_calib_Yc, d_calib_part, d_cam_cand;
   DBuf<int> d_calib_bfwd;        // all-zero Tables::bfwd_start of a handle with free camera coordinates: a camera column is dense, no row of it is skipped
+  // free IMU blocks (kernels_imucal.hpp): allocated by the first prepare() that has one
+  int ni = 0;                    // free IMU coordinates in the system (imu_columns)
+  std::vector<int> imucal_map;   // ni: entry of row 0 of the column inside a record of sensor Jacobians | row stride << 16
+  DBuf<int> d_imucal_map;
+  DBuf<double> d_imucal_rec, d_imucal_part;
   std::vector<hipEvent_t> events;
   hipStream_t side = nullptr;           // second stream: the segment partials run next to the landmark pass (independent inputs)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_irec = nullptr;
@@ -405,6 +411,21 @@ static int camera_columns(const hs_problem* p, std::vector<int>* map) {
       if (used[c] && !p->cam_const[3 * c + b])
         for (int j = 0; j < size[b]; ++j, ++n)
           if (map) map->push_back(c << 8 | (first[b] + j));
+  return n;
+}
+
+/// Border columns of the free IMU coordinates, in the order of hs_reduced_system: the free blocks of [T_bs 6 | i_g 6 | i_a 6 | S_g 9 | X_a 9]
+/// (the layout of inertial_sensor_jacobians). A window without inertial rows has none (Ceres drops parameter blocks without residual
+/// blocks); otherwise every free coordinate stays, all-zero columns included. `map`: nullable.
+static int imu_columns(const hs_problem* p, std::vector<int>* map) {
+  if (map) map->clear();
+  if (p->imu_const.empty() || !p->has_imu || p->in_stamp.empty()) return 0;
+  static const int first[5] = {0, 36, 72, 108, 162}, size[5] = {6, 6, 6, 9, 9};
+  int n = 0;
+  for (int b = 0; b < 5; ++b)
+    if (!p->imu_const[b])
+      for (int j = 0; j < size[b]; ++j, ++n)
+        if (map) map->push_back((first[b] + j) | size[b] << 16);
   return n;
 }
 
@@ -700,7 +721,7 @@ int prepare(hs_problem* p) {
   HIP_TRY(p->d_g_s.reserve(np));
   HIP_TRY(p->d_g_full.reserve(np));
   HIP_TRY(p->d_D2p.reserve(np));
-  HIP_TRY(p->d_gabs.reserve(np + (p->has_imu ? 6 * p->n_bias + 2 : 0) + camera_columns(p, nullptr) + 1));
+  HIP_TRY(p->d_gabs.reserve(np + (p->has_imu ? 6 * p->n_bias + 2 : 0) + imu_columns(p, nullptr) + camera_columns(p, nullptr) + 1));
   HIP_TRY(p->d_step_p.reserve(np));
   HIP_TRY(p->d_delta_p.reserve(np));
   int vis_block = 0;
@@ -725,7 +746,8 @@ int prepare(hs_problem* p) {
     HS_FAIL(HS_ERR_INVALID, "too many free camera coordinates: at most " + std::to_string(kCalibMaxCols) + " per window (kCalibMaxCols), " +
                                 std::to_string(p->nc) + " requested (hs_set_camera_constancy)");
   const int nbi = p->has_imu ? 6 * p->n_bias + 2 : 0;  // bias splines + gravity
-  const int nbd = nbi + p->nc;                          // border unknowns: those, then the free camera coordinates
+  p->ni = imu_columns(p, &p->imucal_map);               // free IMU coordinates (hs_set_imu_constancy): built, not estimated — the limits below do not count them
+  const int nbd = nbi + p->ni + p->nc;                  // border unknowns: those, then the free IMU coordinates, then the free camera coordinates (sizes of the tables)
   // (the two limits below belong to the solver's bordered factorisation — k_border_forward, k_border_solve. A handle that only BUILDS the system
   //  of its free camera coordinates (hs_reduced_system) never reaches them: they count the bias / gravity columns, and the camera columns too
   //  once hs_set_camera_estimation sends them through hs_solve)
@@ -733,9 +755,10 @@ int prepare(hs_problem* p) {
     if (size_t(np) * 8 * 8 > 150 * 1024)
       HS_FAIL(HS_ERR_INVALID, "window too long for the LDS-resident border forward sweep with free camera coordinates: " + std::to_string(p->n_cp) +
                                   " control points, at most " + std::to_string(150 * 1024 / (6 * 8 * 8)) + " (6 n_cp x 8 doubles within 150 KiB)");
-    if (nbd + 1 > 128 && (size_t(nbd + 1) * (nbd + 1) + nbd) * sizeof(double) > size_t(150) * 1024)
+    const int nbe = nbi + p->nc;  // (what the solver would estimate: free IMU coordinates are built only, hs_solve refuses them — not counted)
+    if (nbe + 1 > 128 && (size_t(nbe + 1) * (nbe + 1) + nbe) * sizeof(double) > size_t(150) * 1024)
       HS_FAIL(HS_ERR_INVALID, "too many border unknowns for the LDS-resident dense solve of the border system: " + std::to_string(nbi) +
-                                  " bias / gravity + " + std::to_string(p->nc) + " free camera coordinates = " + std::to_string(nbd) +
+                                  " bias / gravity + " + std::to_string(p->nc) + " free camera coordinates = " + std::to_string(nbe) +
                                   ", at most 137 (hs_set_camera_estimation)");
   }
   if (nbi && size_t(np) * 8 * 8 > 150 * 1024) HS_FAIL(HS_ERR_INVALID, "window too long for the LDS-resident border forward sweep");
@@ -753,6 +776,13 @@ int prepare(hs_problem* p) {
     HIP_TRY(p->d_calib_part.reserve(size_t(std::max(n_parts, 1)) * (p->nc * p->nc + 2 * p->nc)));
     HIP_TRY(p->d_cam_cand.reserve(size_t(kCamStride) * std::max(p->n_cam, 1)));
     HIP_TRY(p->d_calib_bfwd.upload(std::vector<int>((nbd + kBorderCols - 1) / kBorderCols + kSchurTile, 0), s));
+  }
+  if (p->ni) {
+    HIP_TRY(p->d_imucal_map.upload(p->imucal_map, s));
+    HIP_TRY(p->d_imucal_rec.reserve(size_t(n_ine) * kSensorRecInertial));
+    // partials of k_imucal_ii (chunks x jobs), then those of k_imucal_bb (bias points x column groups x slices), 36 doubles each
+    HIP_TRY(p->d_imucal_part.reserve((size_t((n_ine + kImuCalChunk - 1) / kImuCalChunk) * imucal_jobs(p->ni) + size_t(p->n_bias) * imucal_groups(p->ni) * kImuCalBbSlices) *
+                                     kImuCalGroup * kImuCalGroup));
   }
   HIP_TRY(p->d_ybuf.reserve(np));
   HIP_TRY(p->d_scale_b.reserve(nbd + 1));
@@ -882,7 +912,7 @@ int prepare(hs_problem* p) {
   T.bias_g = p->d_bias_g.p, T.bias_a = p->d_bias_a.p, T.bias_g_cand = p->d_bias_g_cand.p, T.bias_a_cand = p->d_bias_a_cand.p;
   T.gravity = p->d_gravity.p, T.gravity_cand = p->d_gravity_cand.p, T.bias_const = p->bias_const, T.gravity_const = p->gravity_const;
   T.inertial_literal = p->inertial_mode == HS_INERTIAL_AS_REFERENCE;
-  T.nb = (p->has_imu ? 6 * p->n_bias + 2 : 0) + p->nc;
+  T.nb = (p->has_imu ? 6 * p->n_bias + 2 : 0) + p->ni + p->nc;
   T.nc = p->nc, T.calib_map = p->d_calib_map.p, T.calib_rec = p->d_calib_rec.p, T.calib_Yc = p->d_calib_Yc.p, T.calib_part = p->d_calib_part.p;
   T.n_seg = n_seg, T.bw = vs.bw, T.np = np;
   T.scale_p = p->d_scale_p.p, T.Sb = p->d_Sb.p, T.Ub = p->d_Ub.p, T.Ubk = p->d_Ubk.p, T.g_s = p->d_g_s.p, T.g_full = p->d_g_full.p, T.D2p = p->d_D2p.p, T.gabs = p->d_gabs.p;

@@ -18,6 +18,7 @@
 //   k_pack_decision -> [all-reduce] -> k_decide -> k_commit      trust-region logic and acceptance
 // Handles with free camera coordinates (kernels_calib.hpp) add k_calib_rows / _landmark / _pc / _cc / _finish behind the landmark factors,
 // k_calib_candidate in front of the update (whose <true> instantiations carry the Y_c dc term) and k_calib_commit behind the decision.
+// Handles with free IMU coordinates (kernels_imucal.hpp) add k_imucal_rows / _pi / _bb / _ii / _finish behind k_border_bb (build only).
 #pragma once
 #include "kernels_common.hpp"
 #include "kernels_linearize.hpp"
@@ -39,3 +40,4 @@
 #include "kernels_klt.hpp"
 #include "kernels_covariance.hpp"
 #include "kernels_calib.hpp"
+#include "kernels_imucal.hpp"

@@ -169,7 +169,7 @@ struct Tables {
   double* gravity_cand;
   int bias_const, gravity_const;
   int inertial_literal;  // Jacobian of the inertial factor as written upstream (inertial.cpp:131-198) | 0: derivative of the prediction
-  int nb;                  // border unknowns: 6 n_bias + 2 (0 without an IMU), then the nc free camera coordinates
+  int nb;                  // border unknowns: 6 n_bias + 2 (0 without an IMU), then the free IMU coordinates (kernels_imucal.hpp), then the nc free camera coordinates
   int nc;                  // free camera coordinates in the system (hs_set_camera_constancy; the last nc border columns, kernels_calib.hpp)
   const int* calib_map;    // nc: camera << 8 | column inside the camera's [T_bs 6 | intrinsics 4 | distortion 4]
   double* calib_rec;       // n_vis x calib_record<K>() (segment-major slots)

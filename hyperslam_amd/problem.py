@@ -69,6 +69,7 @@ class Window:
     inertial_measurements: np.ndarray = field(default_factory=lambda: np.zeros((0, 6)))
     # IMU (optional)
     imu: dict | None = None  # keys: T_bs, i_g, i_a, S_g, X_a, bias_order, bias_t0, bias_dt, bias_g (n x 4), bias_a, bias_constant
+    imu_constant: np.ndarray | None = None  # 5 flags [T_bs, i_g, i_a, S_g, X_a], non-zero = constant; None: every block constant
     gravity: np.ndarray = field(default_factory=lambda: np.array([0.0, 0.0, -9.80665]))
     gravity_constant: bool = True
 
@@ -152,6 +153,10 @@ class Problem:
             bg, ba = _arr(m["bias_g"], _f64, (-1, 4)), _arr(m["bias_a"], _f64, (-1, 4))
             self._check(L.set_imu(h, *[_d(x) for x in a], int(m["bias_order"]), float(m["bias_t0"]), float(m["bias_dt"]), bg.shape[0],
                                   _d(bg), _d(ba), int(m.get("bias_constant", False))), "set_imu")
+        if hasattr(L, "set_imu_constancy"):  # (None: every block constant)
+            self.set_imu_constancy(w.imu_constant)
+        elif w.imu_constant is not None and np.any(np.asarray(w.imu_constant) == 0):
+            raise HsError(f"{L.prefix}set_imu_constancy: not provided by this library (sensor blocks are constant there)")
         g = _arr(w.gravity, _f64, (3,))
         self._check(L.set_gravity(h, _d(g), int(w.gravity_constant)), "set_gravity")
         st, px = _arr(w.pixel_stamps, _f64), _arr(w.pixels, _f64, (-1, 2))
@@ -367,6 +372,16 @@ class Problem:
             return
         c = _arr(constant, np.uint8, (-1, 3))
         self._check(self.lib.set_camera_constancy(self.h, c.shape[0], _u8(c)), "set_camera_constancy")
+
+    def set_imu_constancy(self, constant):
+        """Which IMU blocks stay constant: 5 flags [T_bs, i_g, i_a, S_g, X_a], non-zero = constant; None = all (the default)."""
+        if not hasattr(self.lib, "set_imu_constancy"):
+            raise HsError(f"{self.lib.prefix}set_imu_constancy: not provided by this library (sensor blocks are constant there)")
+        if constant is None:
+            self._check(self.lib.set_imu_constancy(self.h, None), "set_imu_constancy")
+            return
+        c = _arr(constant, np.uint8, (5,))
+        self._check(self.lib.set_imu_constancy(self.h, _u8(c)), "set_imu_constancy")
 
     def set_camera_estimation(self, enabled=True):
         """solve() estimates the free camera blocks of set_camera_constancy on this handle (off by default: solve() refuses them)."""

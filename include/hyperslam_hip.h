@@ -131,7 +131,8 @@ int hs_set_cameras(hs_problem* p, int n, const double* T_bs, const double* intri
 /* Camera blocks the solver may estimate (Manifold<Sensor>::setTransformationConstant, Manifold<Camera>::setIntrinsicsConstant /
  * setDistortionConstant). constant: n x 3 flags [transformation, intrinsics, distortion] per camera, n = the camera count of
  * hs_set_cameras; non-zero keeps the block constant. NULL restores the default: every block constant (camera.hpp:18). A camera table of
- * another size resets the flags. Free coordinates are border unknowns behind bias_g, bias_a and gravity (hs_reduced_system), per camera in
+ * another size resets the flags. Free coordinates are the last border unknowns, behind bias_g, bias_a, gravity and the free IMU coordinates
+ * of hs_set_imu_constancy (hs_reduced_system), per camera in
  * table order the free blocks [T_bs 6 | intrinsics 4 | distortion 4], Ceres-local: T_bs on HS_MANIFOLD_SE3 [d_rot(3) d_trans(3)],
  * intrinsics [cx cy fx fy] and radtan [k1 k2 p1 p2] Euclidean. Pixel residuals touch all three blocks of their camera, bearing residuals
  * T_bs only (their intrinsics / distortion columns are zero). A camera no visual residual references is left out. At most 64 free camera
@@ -165,6 +166,19 @@ int hs_set_landmarks(hs_problem* p, int n, const double* xyz, const uint8_t* con
  * bias splines: uniform R^3 splines of order bias_order, control point j at bias_t0 + j*bias_dt, n_bias x 4 [x y z t]. */
 int hs_set_imu(hs_problem* p, const double* T_bs, const double* i_g, const double* i_a, const double* S_g, const double* X_a,
                int bias_order, double bias_t0, double bias_dt, int n_bias, const double* bias_g, const double* bias_a, int bias_constant);
+/* IMU blocks that enter the reduced system as unknowns (Manifold<Sensor>::setTransformationConstant, Manifold<IMU>::
+ * setGyroscopeIntrinsicsConstant / setAccelerometerIntrinsicsConstant, and the S_g / X_a blocks the inertial evaluator fills next to them,
+ * inertial.cpp:155-194). constant: five flags [T_bs, i_g, i_a, S_g, X_a]; non-zero keeps the block constant. NULL, or
+ * all five set, is the default: every block constant (imu.hpp:18), with the tables, launches and results of a handle that never calls this.
+ * The flags belong to the handle: a later hs_set_imu keeps them. Free coordinates are border unknowns behind gravity and in front of the
+ * free camera coordinates (hs_reduced_system), in the order of the free blocks [T_bs 6 | i_g 6 | i_a 6 | S_g 9 | X_a 9] (at most 36),
+ * Ceres-local: T_bs on HS_MANIFOLD_SE3 [d_rot(3) d_trans(3)], q <- dq(delta) (x) q as for cameras; i_g / i_a [c00 c11 c22 c10 c20 c21] and
+ * S_g / X_a (column-major) Euclidean in the layout of hs_set_imu. Their Jacobians follow hs_set_inertial_jacobian. A window without inertial
+ * residuals leaves the IMU columns out; a coordinate whose column is zero stays, with 1 on its diagonal. This version BUILDS their system
+ * (hs_dim_pose, hs_reduced_system, also through the delta interface); hs_solve and hs_compute_covariance refuse a handle with a free IMU
+ * block (HS_ERR_STATE) whatever hs_set_camera_estimation / hs_set_camera_covariance say, and hs_solve / hs_reduced_system refuse a sharded
+ * handle (world > 1) with one (HS_ERR_STATE). */
+int hs_set_imu_constancy(hs_problem* p, const uint8_t* constant);
 /* Jacobian of the inertial factor. HS_INERTIAL_AS_REFERENCE (default; also HS_REFERENCE_LITERAL=1 in the environment at hs_create)
  * reproduces inertial.cpp:131-198 as written: the linear rows of the state / extrinsic-rotation columns carry I_g where the
  * prediction has I_a (:136,142,148,158), and the S_g / X_a terms of the state, extrinsic and gravity columns are absent (:134-153,
@@ -224,7 +238,7 @@ int hs_residual_layout(hs_problem* p, int type, int idx, int32_t* num_blocks, in
 
 /* ---- evaluation (parity / debugging surface) ------------------------------------------------------------------ */
 int hs_num_residuals(hs_problem* p, int type);
-int hs_dim_pose(hs_problem* p); /* 6*n_cp (+ 6*n_bias + 2 with an IMU) (+ free camera coordinates): size of the reduced system */
+int hs_dim_pose(hs_problem* p); /* 6*n_cp (+ 6*n_bias + 2 with an IMU) (+ free IMU coordinates) (+ free camera coordinates): size of the reduced system */
 /* Batched replacement of ExteroceptiveCost::Evaluate + Ceres' local-Jacobian projection for every residual of `type`.
  * robustify != 0 additionally applies Ceres' loss corrector (sqrt(rho') scaling of r and J). */
 int hs_linearize(hs_problem* p, int type, int robustify, const hs_linearization* out);
@@ -244,7 +258,8 @@ int hs_set_weights(hs_problem* p, int type, const double* weights);
 int hs_cost(hs_problem* p, double* cost);
 /* Reduced (landmark-eliminated), Jacobi-scaled, LM-damped system of the first iteration at the current point:
  * S (dim x dim, row-major, symmetric) and g (dim). What one LM iteration factors; parity target for the Schur build.
- * Columns: control points, then the border: bias_g points, bias_a points, gravity, free camera coordinates (hs_set_camera_constancy). */
+ * Columns: control points, then the border: bias_g points, bias_a points, gravity, free IMU coordinates (hs_set_imu_constancy), free camera
+ * coordinates (hs_set_camera_constancy). */
 int hs_reduced_system(hs_problem* p, double radius, double* S, double* g);
 
 /* ---- marginal covariances (the counterpart of ceres::Covariance) ---------------------------------------- */
