@@ -144,8 +144,10 @@ _PRODUCT_ONLY = {
     # marginal covariances (the oracle has no counterpart)
     # free camera blocks (the oracle keeps every sensor block constant)
     "set_camera_constancy": (C.c_int, [C.c_void_p, C.c_int, c_uint8_p]),
-    # free IMU blocks (the build of their reduced system)
+    # free IMU blocks (the build of their reduced system, their estimation in hs_solve)
     "set_imu_constancy": (C.c_int, [C.c_void_p, c_uint8_p]),
+    "set_imu_estimation": (C.c_int, [C.c_void_p, C.c_int]),
+    "get_imu": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "set_camera_estimation": (C.c_int, [C.c_void_p, C.c_int]),
     "set_camera_covariance": (C.c_int, [C.c_void_p, C.c_int]),
     "get_cameras": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),

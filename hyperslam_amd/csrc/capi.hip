@@ -276,6 +276,39 @@ int hs_set_imu_constancy(hs_problem* p, const uint8_t* constant) {
   return HS_OK;
 }
 
+/// hs_solve estimates the free IMU blocks of this handle (off by default: it refuses them).
+int hs_set_imu_estimation(hs_problem* p, int enabled) {
+  if (!p) return HS_ERR_INVALID;
+  const bool on = enabled != 0;
+  if (on == p->imu_estimation) return HS_OK;
+  p->imu_estimation = on;
+  if (imu_columns(p, nullptr)) p->touch(hs_problem::kTail);  // (routing, the border limits and the tables of prepare() depend on it)
+  return HS_OK;
+}
+
+/// The host copies: hs_solve keeps them equal to the device's parameters.
+int hs_get_imu(hs_problem* p, double* T_bs, double* i_g, double* i_a, double* S_g, double* X_a) {
+  if (!p) return HS_ERR_INVALID;
+  if (!p->has_imu) HS_FAIL(HS_ERR_STATE, "hs_get_imu: no IMU (hs_set_imu has not been called)");
+  if (T_bs) std::memcpy(T_bs, p->imu_T_bs, 56);
+  if (i_g) std::memcpy(i_g, p->imu_i_g, 48);
+  if (i_a) std::memcpy(i_a, p->imu_i_a, 48);
+  if (S_g) std::memcpy(S_g, p->imu_S_g, 72);
+  if (X_a) std::memcpy(X_a, p->imu_X_a, 72);
+  return HS_OK;
+}
+
+static ImuParams pack_imu(const hs_problem* p) {
+  ImuParams ip;
+  std::memcpy(ip.T_bs, p->imu_T_bs, 56), std::memcpy(ip.i_g, p->imu_i_g, 48), std::memcpy(ip.i_a, p->imu_i_a, 48);
+  std::memcpy(ip.S_g, p->imu_S_g, 72), std::memcpy(ip.X_a, p->imu_X_a, 72);
+  return ip;
+}
+static void unpack_imu(hs_problem* p, const ImuParams& ip) {
+  std::memcpy(p->imu_T_bs, ip.T_bs, 56), std::memcpy(p->imu_i_g, ip.i_g, 48), std::memcpy(p->imu_i_a, ip.i_a, 48);
+  std::memcpy(p->imu_S_g, ip.S_g, 72), std::memcpy(p->imu_X_a, ip.X_a, 72);
+}
+
 int hs_set_inertial_jacobian(hs_problem* p, int mode) {
   if (!p) return HS_ERR_INVALID;
   if (mode != HS_INERTIAL_AS_REFERENCE && mode != HS_INERTIAL_EXACT) HS_FAIL(HS_ERR_INVALID, "unknown inertial Jacobian mode");
@@ -976,7 +1009,8 @@ int hs_solve(hs_problem* p, int max_iterations, hs_summary* summary, hs_iteratio
   if (max_iterations < 0 || max_iterations > kMaxIterations) HS_FAIL(HS_ERR_INVALID, "max_iterations out of range");
   if (imu_columns(p, nullptr)) {  // (whatever hs_set_camera_estimation says)
     if (p->world > 1) HS_FAIL(HS_ERR_STATE, kImuShardMessage);
-    HS_FAIL(HS_ERR_STATE, "hs_solve: free IMU blocks (hs_set_imu_constancy) are not supported by the solver in this version; "
+    if (!p->imu_estimation)  // (estimating them is opt-in per handle: hs_set_imu_estimation)
+      HS_FAIL(HS_ERR_STATE, "hs_solve: free IMU blocks (hs_set_imu_constancy) are not supported by the solver in this version; "
                           "hs_reduced_system builds their system (DESIGN.md section 14)");
   }
   if (camera_columns(p, nullptr)) {
@@ -1060,8 +1094,13 @@ int hs_solve(hs_problem* p, int max_iterations, hs_summary* summary, hs_iteratio
   // Estimated cameras: the host table follows the device right here (16 doubles per camera), so hs_get_cameras, the result cache, a later
   // upload of the camera table and the evaluation calls that send it (hs_process_tracks, hs_sample_trajectory) all see the estimate.
   if (p->T.nc && max_iterations > 0) HIP_TRY(hipMemcpyAsync(p->cam.data(), p->d_cam.p, p->cam.size() * 8, hipMemcpyDeviceToHost, s));
+  // Estimated IMU blocks: the host copies (imu_T_bs ..) follow the device the same way, so hs_get_imu, a later upload of the parameters (hs_cost,
+  // hs_linearize, hs_reduced_system, the next hs_solve, the delta interface) and hs_snapshot see the estimate.
+  const bool imu_back = p->imu_estimated() && max_iterations > 0;
+  if (imu_back) HIP_TRY(hipMemcpyAsync(&p->imu_readback, p->d_imu.p, sizeof(ImuParams), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(&st, p->d_state.p, sizeof(st), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  if (imu_back) unpack_imu(p, p->imu_readback);
   if (max_iterations > 0) p->device_ahead = true;
   p->results_cached = p->want_results;  // only once every copy above has completed: a failed copy or synchronisation leaves the getters on the device path
   if (p->host_timing) {
@@ -1133,6 +1172,8 @@ int hs_snapshot(hs_problem* p) {
     HIP_TRY(hipMemcpyAsync(p->d_gravity_snap.p, p->d_gravity.p, 24, hipMemcpyDeviceToDevice, p->stream));
   }
   p->cam_snap = p->cam;  // (the host table equals the device's: hs_solve keeps it so)
+  if (p->has_imu) p->imu_snap = pack_imu(p);  // (likewise)
+  p->has_imu_snap = p->has_imu;
   p->has_snapshot = true;
   return HS_OK;
 }
@@ -1153,6 +1194,14 @@ int hs_restore(hs_problem* p) {
     p->cam = p->cam_snap;
     HIP_TRY(hipMemcpyAsync(p->d_cam.p, p->cam.data(), p->cam.size() * 8, hipMemcpyHostToDevice, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
+  }
+  if (p->has_imu && p->has_imu_snap) {
+    const ImuParams now = pack_imu(p);
+    if (std::memcmp(&now, &p->imu_snap, sizeof(ImuParams)) != 0) {  // IMU blocks estimated since the snapshot
+      unpack_imu(p, p->imu_snap);
+      HIP_TRY(hipMemcpyAsync(p->d_imu.p, &p->imu_snap, sizeof(ImuParams), hipMemcpyHostToDevice, p->stream));
+      HIP_TRY(hipStreamSynchronize(p->stream));
+    }
   }
   return HS_OK;
 }

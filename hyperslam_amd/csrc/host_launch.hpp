@@ -126,6 +126,7 @@ static bool factor_two_ended_any(const hs_problem* p) {
   const bool la_ok = !(T.debug_flags & 4) && la_compute_waves(T.bw) > 0;
   const int nt = HS_AB(T.debug_flags, 131072) ? mfma_window_tiles(T.bw) : 0;
   if (T.nc) return false;  // free camera coordinates: always one-ended (k_dense_solve_mx, or the band kernels + k_border_forward / _schur / _solve / _apply)
+  if (p->imu_estimated()) return false;  // estimated IMU coordinates (hs_set_imu_estimation): dense columns too, the same route
   return (la_ok || nt) && (T.nb == 0 || (!nt && !(T.debug_flags & 536870912) && (T.nb + kBorderCols - 1) / kBorderCols <= 512)) && n_blk >= 4 * T.bw && T.Sb2 &&
          !(T.debug_flags & 2048);  // (512: flag words of k_border_forward2's column groups)
 }
@@ -558,7 +559,8 @@ int launch_factor(hs_problem* p) {
     // the first non-zero row of a border column follows from the inertial record table — of ALL shards: a shard of a distributed solve
     // only skips the rows of the constant control points (which every shard agrees on)
     // (a free camera column is dense over every control point with visual rows: no row of it is skipped either — its bfwd_start is zero)
-    const int local_rows = (!p->allreduce && !p->rccl_comm && p->world == 1 && !T.nc) ? 1 : 0;
+    // (nor is a row of an estimated IMU column, dense over every control point an inertial record reaches)
+    const int local_rows = (!p->allreduce && !p->rccl_comm && p->world == 1 && !T.nc && !p->imu_estimated()) ? 1 : 0;
     k_border_forward<<<(T.nb + kBorderCols - 1) / kBorderCols, fwd_threads, size_t(T.np) * kBorderLd * sizeof(double), s>>>(T, f0, local_rows);
     const int nt = (T.nb + kSchurTile - 1) / kSchurTile;
     k_border_schur<<<dim3(nt, nt), kBlock, 0, s>>>(T, f0, local_rows, n_blk);
@@ -641,23 +643,31 @@ int launch_update(hs_problem* p, bool linearize_candidate = false, bool deferred
   // Free camera coordinates (hs_set_camera_estimation): k_calib_candidate retracts the candidate camera table from the border step in front of
   // the update; the kernels that evaluate the candidate's visual cost get that table as T.cam (Tc). Its norms are one more pair behind the
   // norm workgroups' (slot n_norm_part), which only the decision kernel counts (Td).
-  Tables calib_tables[2];  // (filled for a handle with free camera coordinates only)
+  // Estimated IMU coordinates (hs_set_imu_estimation) likewise: k_imucal_candidate retracts the candidate IMU parameters, the kernels that
+  // evaluate the candidate's inertial cost get them as T.imu (the same copy Tc), and their norms are the pair behind the camera blocks'.
+  Tables calib_tables[2];  // (filled for a handle with free camera coordinates or estimated IMU coordinates only)
+  const bool est_i = p->imu_estimated(), sensors = T.nc || est_i;
+  if (sensors) calib_tables[0] = calib_tables[1] = T;
   if (T.nc) {
     k_calib_candidate<<<1, kBlock, 0, s>>>(T, p->d_cam_cand.p, T.n_norm_part);
-    calib_tables[0] = calib_tables[1] = T;
-    calib_tables[0].cam = p->d_cam_cand.p, calib_tables[1].n_norm_part = T.n_norm_part + 1;
+    calib_tables[0].cam = p->d_cam_cand.p, calib_tables[1].n_norm_part += 1;
   }
-  const Tables &Tc = T.nc ? calib_tables[0] : T, &Td = T.nc ? calib_tables[1] : T;
+  if (est_i) {
+    const ImuCal A{nullptr, p->d_imucal_map.p, nullptr, nullptr, p->ni, 6 * T.n_bias + 2};
+    k_imucal_candidate<<<1, kBlock, 0, s>>>(T, A, p->d_imu_cand.p, calib_tables[1].n_norm_part);
+    calib_tables[0].imu = p->d_imu_cand.p, calib_tables[1].n_norm_part += 1;
+  }
+  const Tables &Tc = sensors ? calib_tables[0] : T, &Td = sensors ? calib_tables[1] : T;
   if (p->fused) {  // candidate point, landmark back-substitution and the visual candidate cost per chunk, one launch
     const int nb_pri = merged && T.n_pri ? p->nb_pri : 0, nb_ine = merged && T.n_ine ? p->nb_ine : 0;
     const size_t lds = std::max(size_t(update_lds_doubles(T.bw, p->build_R, p->build_L)), size_t(8 * T.sp.n_cp + 8 * T.n_bias + 4)) * 8;
     if (T.nc)
       k_update_visual<K, true><<<p->nb_vis + T.n_norm_part + nb_pri + nb_ine, kBlock, lds, s>>>(Tc, p->build_R, p->build_L, p->nb_vis, nb_pri, nb_ine);
     else
-      k_update_visual<K><<<p->nb_vis + T.n_norm_part + nb_pri + nb_ine, kBlock, lds, s>>>(T, p->build_R, p->build_L, p->nb_vis, nb_pri, nb_ine);
+      k_update_visual<K><<<p->nb_vis + T.n_norm_part + nb_pri + nb_ine, kBlock, lds, s>>>(Tc, p->build_R, p->build_L, p->nb_vis, nb_pri, nb_ine);
     if (T.n_pri && !merged) k_cost_prior<K><<<p->nb_pri, kBlock, cp_lds_bytes(p), s>>>(T, T.cp_cand, T.cand_part + p->nb_vis);
     if (T.n_ine && !merged)
-      k_cost_inertial<K, 4><<<p->nb_ine, kInertialBlock, cp_lds_bytes(p), s>>>(T, T.cp_cand, T.bias_g_cand, T.bias_a_cand, T.gravity_cand,
+      k_cost_inertial<K, 4><<<p->nb_ine, kInertialBlock, cp_lds_bytes(p), s>>>(Tc, T.cp_cand, T.bias_g_cand, T.bias_a_cand, T.gravity_cand,
                                                                           T.cand_part + p->nb_vis + p->nb_pri);
   } else if (T.nc)
     k_backsub_retract<true><<<T.n_lm_part + T.n_norm_part, kBlock, 0, s>>>(T);
@@ -675,7 +685,7 @@ int launch_update(hs_problem* p, bool linearize_candidate = false, bool deferred
     if (T.n_vis) k_cost_visual<K><<<p->nb_vis, kBlock, cp_lds_bytes(p), s>>>(Tc, T.cp_cand, T.lm_cand, T.cand_part);
     if (T.n_pri) k_cost_prior<K><<<p->nb_pri, kBlock, cp_lds_bytes(p), s>>>(T, T.cp_cand, T.cand_part + p->nb_vis);
     if (T.n_ine)
-      k_cost_inertial<K, 4><<<p->nb_ine, kInertialBlock, cp_lds_bytes(p), s>>>(T, T.cp_cand, T.bias_g_cand, T.bias_a_cand, T.gravity_cand,
+      k_cost_inertial<K, 4><<<p->nb_ine, kInertialBlock, cp_lds_bytes(p), s>>>(Tc, T.cp_cand, T.bias_g_cand, T.bias_a_cand, T.gravity_cand,
                                                                           T.cand_part + p->nb_vis + p->nb_pri);
   }
   if (fold_next) return HS_OK;  // (fold_decision_into_build: the next iteration's k_build_visual decides, launch_build(..., fold = true))
@@ -689,6 +699,7 @@ int launch_update(hs_problem* p, bool linearize_candidate = false, bool deferred
   //  hs_solve launches k_commit once behind the last iteration)
   if (!inline_commit && !deferred_commit) k_commit<<<nb_commit, kBlock, 0, s>>>(T);
   if (T.nc) k_calib_commit<<<1, kBlock, 0, s>>>(T, p->d_cam.p, p->d_cam_cand.p);  // an accepted step: cam <- candidate cameras
+  if (est_i) k_imucal_commit<<<1, kBlock, 0, s>>>(T, p->d_imu.p, p->d_imu_cand.p);  // ... and imu <- candidate IMU parameters
   HIP_TRY(hipGetLastError());
   return HS_OK;
 }

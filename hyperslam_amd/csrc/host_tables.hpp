@@ -334,12 +334,18 @@ struct hs_problem {
   std::vector<int> calib_map;    // nc: camera << 8 | column inside the camera's 14
   DBuf<int> d_calib_map;
   DBuf<double> d_calib_rec, d_calib_Yc, d_calib_part, d_cam_cand;
-  DBuf<int> d_calib_bfwd;        // all-zero Tables::bfwd_start of a handle with free camera coordinates: a camera column is dense, no row of it is skipped
+  DBuf<int> d_calib_bfwd;        // all-zero Tables::bfwd_start of a handle with free camera coordinates (or estimated IMU coordinates): such a column is dense, no row of it is skipped
   // free IMU blocks (kernels_imucal.hpp): allocated by the first prepare() that has one
   int ni = 0;                    // free IMU coordinates in the system (imu_columns)
   std::vector<int> imucal_map;   // ni: entry of row 0 of the column inside a record of sensor Jacobians | row stride << 16
   DBuf<int> d_imucal_map;
   DBuf<double> d_imucal_rec, d_imucal_part;
+  bool imu_estimation = false;   // hs_set_imu_estimation: hs_solve estimates the free blocks (off: it refuses a handle that has one)
+  bool imu_estimated() const { return ni > 0 && imu_estimation; }  // (ni: as of the last prepare())
+  DBuf<ImuParams> d_imu_cand;    // candidate IMU parameters next to d_imu (k_imucal_candidate), on handles that estimate IMU blocks only
+  ImuParams imu_readback;        // hs_solve: the device parameters on their way into the host copies (imu_T_bs ..)
+  ImuParams imu_snap;            // hs_snapshot: the five blocks (host copies; hs_solve keeps them equal to the device's)
+  bool has_imu_snap = false;
   std::vector<hipEvent_t> events;
   hipStream_t side = nullptr;           // second stream: the segment partials run next to the landmark pass (independent inputs)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_irec = nullptr;
@@ -740,22 +746,32 @@ int prepare(hs_problem* p) {
   HIP_TRY(p->d_ch_gmax.reserve(size_t(p->nb_vis) + 1));
   HIP_TRY(p->d_cand_part.reserve(p->nb_vis + p->nb_pri + p->nb_ine + 1));
   const int nb_norm = p->nb_cp;
-  HIP_TRY(p->d_norm_part.reserve(2 * size_t(nb_norm) + 2));  // (+ the camera blocks' pair, k_calib_candidate)
+  HIP_TRY(p->d_norm_part.reserve(2 * size_t(nb_norm) + 4));  // (+ the camera blocks' pair, k_calib_candidate, + the IMU blocks', k_imucal_candidate)
   p->nc = camera_columns(p, &p->calib_map);
   if (p->nc > kCalibMaxCols)
     HS_FAIL(HS_ERR_INVALID, "too many free camera coordinates: at most " + std::to_string(kCalibMaxCols) + " per window (kCalibMaxCols), " +
                                 std::to_string(p->nc) + " requested (hs_set_camera_constancy)");
   const int nbi = p->has_imu ? 6 * p->n_bias + 2 : 0;  // bias splines + gravity
-  p->ni = imu_columns(p, &p->imucal_map);               // free IMU coordinates (hs_set_imu_constancy): built, not estimated — the limits below do not count them
+  p->ni = imu_columns(p, &p->imucal_map);               // free IMU coordinates (hs_set_imu_constancy): the limits below count them once hs_set_imu_estimation is on
   const int nbd = nbi + p->ni + p->nc;                  // border unknowns: those, then the free IMU coordinates, then the free camera coordinates (sizes of the tables)
   // (the two limits below belong to the solver's bordered factorisation — k_border_forward, k_border_solve. A handle that only BUILDS the system
   //  of its free camera coordinates (hs_reduced_system) never reaches them: they count the bias / gravity columns, and the camera columns too
-  //  once hs_set_camera_estimation sends them through hs_solve)
-  if (p->nc && p->cam_estimation) {
+  //  once hs_set_camera_estimation sends them through hs_solve, the IMU columns once hs_set_imu_estimation does)
+  const bool est_i = p->imu_estimated(), est_c = p->nc && p->cam_estimation;
+  if (est_i) {
+    if (size_t(np) * 8 * 8 > 150 * 1024)
+      HS_FAIL(HS_ERR_INVALID, "window too long for the LDS-resident border forward sweep with free IMU coordinates: " + std::to_string(p->n_cp) +
+                                  " control points, at most " + std::to_string(150 * 1024 / (6 * 8 * 8)) + " (6 n_cp x 8 doubles within 150 KiB)");
+    const int nce = est_c ? p->nc : 0, nbe = nbi + p->ni + nce;  // (what the solver would estimate)
+    if (nbe + 1 > 128 && (size_t(nbe + 1) * (nbe + 1) + nbe) * sizeof(double) > size_t(150) * 1024)
+      HS_FAIL(HS_ERR_INVALID, "too many border unknowns for the LDS-resident dense solve of the border system: " + std::to_string(nbi) +
+                                  " bias / gravity + " + std::to_string(p->ni) + " free IMU coordinates + " + std::to_string(nce) +
+                                  " free camera coordinates = " + std::to_string(nbe) + ", at most 137 (hs_set_imu_estimation)");
+  } else if (est_c) {
     if (size_t(np) * 8 * 8 > 150 * 1024)
       HS_FAIL(HS_ERR_INVALID, "window too long for the LDS-resident border forward sweep with free camera coordinates: " + std::to_string(p->n_cp) +
                                   " control points, at most " + std::to_string(150 * 1024 / (6 * 8 * 8)) + " (6 n_cp x 8 doubles within 150 KiB)");
-    const int nbe = nbi + p->nc;  // (what the solver would estimate: free IMU coordinates are built only, hs_solve refuses them — not counted)
+    const int nbe = nbi + p->nc;  // (what the solver would estimate: without hs_set_imu_estimation hs_solve refuses free IMU coordinates — not counted)
     if (nbe + 1 > 128 && (size_t(nbe + 1) * (nbe + 1) + nbe) * sizeof(double) > size_t(150) * 1024)
       HS_FAIL(HS_ERR_INVALID, "too many border unknowns for the LDS-resident dense solve of the border system: " + std::to_string(nbi) +
                                   " bias / gravity + " + std::to_string(p->nc) + " free camera coordinates = " + std::to_string(nbe) +
@@ -775,14 +791,16 @@ int prepare(hs_problem* p) {
     const int n_parts = (n_vis + kCalibRowChunk - 1) / kCalibRowChunk + (p->n_lm + kCalibLmChunk - 1) / kCalibLmChunk;
     HIP_TRY(p->d_calib_part.reserve(size_t(std::max(n_parts, 1)) * (p->nc * p->nc + 2 * p->nc)));
     HIP_TRY(p->d_cam_cand.reserve(size_t(kCamStride) * std::max(p->n_cam, 1)));
-    HIP_TRY(p->d_calib_bfwd.upload(std::vector<int>((nbd + kBorderCols - 1) / kBorderCols + kSchurTile, 0), s));
   }
+  if (p->nc || est_i)  // (dense border columns: no row of them is skipped)
+    HIP_TRY(p->d_calib_bfwd.upload(std::vector<int>((nbd + kBorderCols - 1) / kBorderCols + kSchurTile, 0), s));
   if (p->ni) {
     HIP_TRY(p->d_imucal_map.upload(p->imucal_map, s));
     HIP_TRY(p->d_imucal_rec.reserve(size_t(n_ine) * kSensorRecInertial));
     // partials of k_imucal_ii (chunks x jobs), then those of k_imucal_bb (bias points x column groups x slices), 36 doubles each
     HIP_TRY(p->d_imucal_part.reserve((size_t((n_ine + kImuCalChunk - 1) / kImuCalChunk) * imucal_jobs(p->ni) + size_t(p->n_bias) * imucal_groups(p->ni) * kImuCalBbSlices) *
                                      kImuCalGroup * kImuCalGroup));
+    if (est_i) HIP_TRY(p->d_imu_cand.reserve(1));
   }
   HIP_TRY(p->d_ybuf.reserve(np));
   HIP_TRY(p->d_scale_b.reserve(nbd + 1));
@@ -939,7 +957,7 @@ int prepare(hs_problem* p) {
     T.Sb2 = need ? p->d_Sb2.p : nullptr, T.g2 = need ? p->d_g2.p : nullptr;
   }
   T.scale_b = p->d_scale_b.p, T.Spb = p->d_Spb.p, T.Sbb = p->d_Sbb.p, T.gb_s = p->d_gb_s.p, T.D2b = p->d_D2b.p;
-  T.Zb = p->d_Zb.p, T.Cb = p->d_Cb.p, T.hb = p->d_hb.p, T.xb = p->d_xb.p, T.delta_b = p->d_delta_b.p, T.i_bias_ptr = p->d_i_bias_ptr.p, T.bfwd_start = p->nc ? p->d_calib_bfwd.p : p->d_bfwd_start.p;
+  T.Zb = p->d_Zb.p, T.Cb = p->d_Cb.p, T.hb = p->d_hb.p, T.xb = p->d_xb.p, T.delta_b = p->d_delta_b.p, T.i_bias_ptr = p->d_i_bias_ptr.p, T.bfwd_start = (p->nc || est_i) ? p->d_calib_bfwd.p : p->d_bfwd_start.p;
   T.x_count1 = x_count1, T.xo_dec = x_count1, T.xo_cdj = x_count0;
   T.fused = p->fused ? 1 : 0, T.n_chunk = p->fused ? p->n_group_wg : 0, T.ch_ptr = p->d_ch_ptr.p, T.ch_desc = p->d_ch_desc.p;
   T.build_stream_lg = p->fused ? build_streams_packed(vs.bw, k) : 0;

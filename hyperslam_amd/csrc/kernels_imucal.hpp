@@ -295,4 +295,53 @@ __global__ void __launch_bounds__(kBlock) k_imucal_finish(Tables T, ImuCal A, in
   Hbb[size_t(A.col0 + ca) * nb + A.col0 + cb] = s, Hbb[size_t(A.col0 + cb) * nb + A.col0 + ca] = s;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Solve side (hs_set_imu_estimation): the candidate IMU parameters and the commit of an accepted step. Both are one-workgroup launches of
+// their own on handles that estimate IMU blocks; handles without launch neither.
+// ---------------------------------------------------------------------------------------------------------------------
+
+constexpr int kImuParamDoubles = int(sizeof(ImuParams) / sizeof(double));  // [T_bs 7 | i_g 6 | i_a 6 | S_g 9 | X_a 9]
+static_assert(kImuParamDoubles == 37 && kImuParamDoubles <= kBlock, "ImuParams is 37 doubles, copied one per lane");
+
+/// Candidate IMU parameters from the unscaled border step di = T.delta_b[A.col0 ..]: *cand (a buffer next to *T.imu that only the launches of a
+/// handle that estimates IMU blocks know: Tables keeps the layout every other kernel was compiled for) = *T.imu with every free block
+/// retracted — T_bs on Product(EigenQuaternion, R3) (q <- dq(d_rot) (x) q, p <- p + d_trans), i_g, i_a, S_g, X_a Euclidean in the parameter
+/// layout. One lane per IMU column (ni <= 36) through the column map (entry of row 0 inside a record of sensor Jacobians: T_bs from 0, i_g 36,
+/// i_a 72, S_g 108, X_a 162); the lane of the T_bs block's first column retracts the block. Also the IMU blocks' share of the decision:
+/// T.norm_part[2 norm_slot ..] = (|x|^2, |x+ - x|^2) over the ambient coordinates of the free blocks, summed in lane order per wave, waves in
+/// index order. No gradient term: the IMU block is not a Schur complement, T.gb_s holds the full gradient on these columns.
+__global__ void __launch_bounds__(kBlock) k_imucal_candidate(Tables T, ImuCal A, ImuParams* cand, int norm_slot) {
+  if (T.st->done) return;
+  __shared__ double red[2 * (kBlock / 64)];
+  const int tid = threadIdx.x;
+  const double* x = reinterpret_cast<const double*>(T.imu);
+  double* y = reinterpret_cast<double*>(cand);
+  if (tid < kImuParamDoubles) y[tid] = x[tid];
+  __syncthreads();
+  double v[2] = {0.0, 0.0};  // |x|^2, |x+ - x|^2
+  if (tid < A.ni) {
+    const int o = A.map[tid] & 0xffff;
+    const double* d = T.delta_b + A.col0 + tid;
+    if (o == 0) {  // T_bs: its six columns are consecutive
+      const Quat q = quat_plus(Quat{x[0], x[1], x[2], x[3]}, V3{d[0], d[1], d[2]});
+      y[0] = q.x, y[1] = q.y, y[2] = q.z, y[3] = q.w, y[4] = x[4] + d[3], y[5] = x[5] + d[4], y[6] = x[6] + d[5];
+#pragma unroll
+      for (int c = 0; c < 7; ++c) v[0] = fma(x[c], x[c], v[0]), v[1] = fma(y[c] - x[c], y[c] - x[c], v[1]);
+    } else if (o >= 36) {  // i_g at 7 .., i_a at 13 .., S_g at 19 .., X_a at 28 .. of the parameter layout
+      const int at = o < 72 ? 7 + (o - 36) : o < 108 ? 13 + (o - 72) : o < 162 ? 19 + (o - 108) : 28 + (o - 162);
+      const double xv = x[at], yv = xv + d[0];
+      y[at] = yv;
+      v[0] = xv * xv, v[1] = (yv - xv) * (yv - xv);
+    }
+  }
+  block_sum_n<2>(v, red);
+  if (tid == 0) T.norm_part[2 * norm_slot] = v[0], T.norm_part[2 * norm_slot + 1] = v[1];
+}
+
+/// *imu <- candidate when the step was accepted (k_commit's rule: `accepted` is read even when a convergence test just ended the solve).
+__global__ void __launch_bounds__(kBlock) k_imucal_commit(Tables T, ImuParams* imu, const ImuParams* cand) {
+  if (!T.st->accepted) return;
+  if (threadIdx.x < kImuParamDoubles) reinterpret_cast<double*>(imu)[threadIdx.x] = reinterpret_cast<const double*>(cand)[threadIdx.x];
+}
+
 }  // namespace hs

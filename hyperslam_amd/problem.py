@@ -383,6 +383,22 @@ class Problem:
         c = _arr(constant, np.uint8, (5,))
         self._check(self.lib.set_imu_constancy(self.h, _u8(c)), "set_imu_constancy")
 
+    def set_imu_estimation(self, enabled=True):
+        """solve() estimates the free IMU blocks of set_imu_constancy on this handle (off by default: solve() refuses them)."""
+        if not hasattr(self.lib, "set_imu_estimation"):
+            if not enabled:
+                return  # (off is what a library without the entry point does anyway)
+            raise HsError(f"{self.lib.prefix}set_imu_estimation: not provided by this library (sensor blocks are constant there)")
+        self._check(self.lib.set_imu_estimation(self.h, int(bool(enabled))), "set_imu_estimation")
+
+    def imu(self):
+        """Current IMU parameters: dict(T_bs (7), i_g (6), i_a (6), S_g (9), X_a (9)) in the layout of the window's imu table."""
+        if not hasattr(self.lib, "get_imu"):
+            raise HsError(f"{self.lib.prefix}get_imu: not provided by this library (sensor blocks are constant there)")
+        out = dict(T_bs=np.zeros(7), i_g=np.zeros(6), i_a=np.zeros(6), S_g=np.zeros(9), X_a=np.zeros(9))
+        self._check(self.lib.get_imu(self.h, *[_d(out[k]) for k in ("T_bs", "i_g", "i_a", "S_g", "X_a")]), "get_imu")
+        return out
+
     def set_camera_estimation(self, enabled=True):
         """solve() estimates the free camera blocks of set_camera_constancy on this handle (off by default: solve() refuses them)."""
         if not hasattr(self.lib, "set_camera_estimation"):

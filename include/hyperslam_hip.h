@@ -174,11 +174,26 @@ int hs_set_imu(hs_problem* p, const double* T_bs, const double* i_g, const doubl
  * free camera coordinates (hs_reduced_system), in the order of the free blocks [T_bs 6 | i_g 6 | i_a 6 | S_g 9 | X_a 9] (at most 36),
  * Ceres-local: T_bs on HS_MANIFOLD_SE3 [d_rot(3) d_trans(3)], q <- dq(delta) (x) q as for cameras; i_g / i_a [c00 c11 c22 c10 c20 c21] and
  * S_g / X_a (column-major) Euclidean in the layout of hs_set_imu. Their Jacobians follow hs_set_inertial_jacobian. A window without inertial
- * residuals leaves the IMU columns out; a coordinate whose column is zero stays, with 1 on its diagonal. This version BUILDS their system
- * (hs_dim_pose, hs_reduced_system, also through the delta interface); hs_solve and hs_compute_covariance refuse a handle with a free IMU
- * block (HS_ERR_STATE) whatever hs_set_camera_estimation / hs_set_camera_covariance say, and hs_solve / hs_reduced_system refuse a sharded
- * handle (world > 1) with one (HS_ERR_STATE). */
+ * residuals leaves the IMU columns out; a coordinate whose column is zero stays, with 1 on its diagonal. hs_dim_pose and hs_reduced_system
+ * (also through the delta interface) BUILD their system; hs_solve estimates the free blocks once hs_set_imu_estimation has enabled it on the
+ * handle and by default refuses a handle with a free IMU block (HS_ERR_STATE) whatever hs_set_camera_estimation says. hs_compute_covariance
+ * refuses such a handle (HS_ERR_STATE) whatever hs_set_camera_covariance says, and hs_solve / hs_reduced_system refuse a sharded handle
+ * (world > 1) with one (HS_ERR_STATE). */
 int hs_set_imu_constancy(hs_problem* p, const uint8_t* constant);
+/* hs_solve estimates the free IMU blocks of hs_set_imu_constancy on this handle (enabled != 0). Off by default: hs_solve then refuses a handle
+ * with a free IMU block exactly as before (HS_ERR_STATE), whatever hs_set_camera_estimation says. On: a handle whose free blocks are IMU blocks
+ * only is solved; one that has free camera blocks as well needs hs_set_camera_estimation too (otherwise the camera refusal). Still refused:
+ * sharded handles (world > 1), a weight matrix, hs_compute_covariance. An accepted step moves the IMU parameters like every other variable:
+ * hs_get_imu, hs_cost, hs_linearize, hs_reduced_system, a later hs_solve and the delta interface see the estimate, hs_snapshot / hs_restore
+ * cover the five blocks, hs_set_imu overrides them (and keeps the flags). Such a window is solved one-ended with the IMU coordinates as border
+ * columns; the border (bias / gravity + free IMU coordinates + the free camera coordinates of hs_set_camera_estimation) is limited to 137
+ * unknowns and the window to 400 control points (HS_ERR_INVALID from the call that prepares the tables, naming the counts): a window with 17
+ * bias control points (104 bias / gravity unknowns) has room for 33 of the 36 IMU coordinates. Handles without a free IMU coordinate are not
+ * affected by the switch; toggling it re-prepares the tables. DESIGN.md section 14. */
+int hs_set_imu_estimation(hs_problem* p, int enabled);
+/* Current IMU parameters in the layout of hs_set_imu: T_bs[7], i_g[6], i_a[6], S_g[9], X_a[9]. Each pointer may be NULL. HS_ERR_STATE on a
+ * handle without an IMU. */
+int hs_get_imu(hs_problem* p, double* T_bs, double* i_g, double* i_a, double* S_g, double* X_a);
 /* Jacobian of the inertial factor. HS_INERTIAL_AS_REFERENCE (default; also HS_REFERENCE_LITERAL=1 in the environment at hs_create)
  * reproduces inertial.cpp:131-198 as written: the linear rows of the state / extrinsic-rotation columns carry I_g where the
  * prediction has I_a (:136,142,148,158), and the S_g / X_a terms of the state, extrinsic and gravity columns are absent (:134-153,
@@ -292,7 +307,9 @@ int hs_sample_covariance(hs_problem* p, int n, const double* stamps, double* cov
 
 /* ---- solve ------------------------------------------------------------------------------------------------------ */
 /* Replaces CeresOptimizer::optimize (optimizer.cpp:276-280) with the options of optimizer.cpp:38-54 (trust-region LM,
- * Jacobi scaling, monotonic steps). iterations (nullable) receives max_iterations + 1 records (record 0 = initial point). */
+ * Jacobi scaling, monotonic steps). iterations (nullable) receives max_iterations + 1 records (record 0 = initial point).
+ * Free sensor blocks are estimated only on a handle that asked for it: free camera blocks with hs_set_camera_estimation, free IMU blocks with
+ * hs_set_imu_estimation (both for a handle that has both); otherwise a handle with one is refused (HS_ERR_STATE). */
 int hs_solve(hs_problem* p, int max_iterations, hs_summary* summary, hs_iteration* iterations);
 /* Per-stage device times in the summary: linearize_ms / schur_ms / solve_ms / update_ms. Off by default — the four HIP events per
  * iteration that bracket the stages are barrier packets on the launch stream and cost ~5.7 us each on gfx950 (7 % of a configs[1]
