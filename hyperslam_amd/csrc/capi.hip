@@ -768,12 +768,8 @@ int hs_cost(hs_problem* p, double* cost) {
   if (rc) return rc;
   rc = reset_state(p, 0, 1e4);
   if (rc) return rc;
-  HS_ORDER_SWITCH(p->k, rc = launch_linearize<K>(p, false, true));
+  rc = launch_cost_only(p);
   if (rc) return rc;
-  k_pack_exchange<<<1, kBlock, 0, p->stream>>>(p->T, 0);
-  rc = exchange(p, p->T.xbuf + p->T.xo_cost, 1);
-  if (rc) return rc;
-  k_cost_reduce<<<1, kBlock, 0, p->stream>>>(p->T);
   HIP_TRY(hipGetLastError());
   DevState st;
   HIP_TRY(hipMemcpyAsync(&st, p->d_state.p, sizeof(st), hipMemcpyDeviceToHost, p->stream));
@@ -1026,7 +1022,7 @@ int hs_solve(hs_problem* p, int max_iterations, hs_summary* summary, hs_iteratio
   const bool spec = speculative_solve(p);
   // (fused visual-only windows defer also when they are small enough for the decision kernel to commit inline: deferred landmarks are what lets the
   //  decision ride in the next build — one launch less per iteration, which at the replay's window sizes is 6 us of 130)
-  const bool deferred = (fused_visual_only(p) || (spec && !commit_inline(p))) && !(p->T.debug_flags & 67108864);  // A/B switch 67108864: k_commit in every iteration
+  const bool deferred = (fused_visual_only(p) || (spec && !commit_inline(p))) && !switch_on(p->T, sw::commit_always);  // (switch commit_always: k_commit in every iteration)
   const bool fold = fold_decision_into_build(p, deferred);  // the decision of iteration i rides in k_build_visual of iteration i + 1
   rc = reset_state(p, max_iterations, 1e4, spec ? (deferred ? 2 : 1) : (deferred ? 4 : 0));
   if (rc) return rc;
@@ -1065,12 +1061,8 @@ int hs_solve(hs_problem* p, int max_iterations, hs_summary* summary, hs_iteratio
     if (stages || it + 1 == max_iterations) HIP_TRY(hipEventRecord(ev[4 * it + 4], s));
   }
   if (max_iterations == 0) {
-    HS_ORDER_SWITCH(p->k, rc = launch_linearize<K>(p, false, true));
+    rc = launch_cost_only(p);
     if (rc) return rc;
-    k_pack_exchange<<<1, kBlock, 0, s>>>(p->T, 0);
-    rc = exchange(p, p->T.xbuf + p->T.xo_cost, 1);
-    if (rc) return rc;
-    k_cost_reduce<<<1, kBlock, 0, s>>>(p->T);
   }
   DevState& st = *p->h_state;
   const auto host_t4 = std::chrono::steady_clock::now();

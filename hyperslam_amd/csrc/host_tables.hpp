@@ -362,9 +362,14 @@ static const char* kWeightsMessage =
     "a weight matrix is set (hs_set_weights): weights are applied by hs_linearize / hs_cost_function_evaluate; the solver runs the "
     "reference's production configuration, weights = nullptr (optimizer.cpp:191,214,236,255)";
 
-/// Measurement switches that select a kernel kept for A/B comparison only: compile-time false in the product library (HS_PROFILE_HOOKS = 0,
-/// the alternatives are not compiled in), HS_DEBUG_FLAGS bits in profiling builds (tools/build_profiling_lib.sh).
-#define HS_AB(flags, bit) (HS_PROFILE_HOOKS && ((flags) & (bit)))
+/// Measurement switches that select a kernel kept for A/B comparison only ("profiling" in switches.hpp): compile-time false in the product
+/// library (HS_PROFILE_HOOKS = 0, the alternatives are not compiled in), HS_DEBUG_FLAGS bits in profiling builds (tools/build_profiling_lib.sh).
+#define HS_AB(T, s) (HS_PROFILE_HOOKS && switch_on(T, s))
+
+/// The look-ahead factorisation k_band_factor_la has an instantiation for this band (3 or 4 compute waves); la_ok: and is not switched off.
+/// (prepare() asks the first alone: the reversed copy of the system is kept whatever the switches say.)
+static bool la_kernel_fits(int bw) { return la_compute_waves(bw) > 0; }
+static bool la_ok(const Tables& T) { return !switch_on(T, sw::factor_legacy) && la_kernel_fits(T.bw); }
 
 /// Spline orders the device kernels are instantiated for: 4, 5 and 6. Runs the statement(s) with the compile-time constant K = k.
 #define HS_ORDER_SWITCH(k, ...)    \
@@ -947,13 +952,13 @@ int prepare(hs_problem* p) {
   T.fj[0] = FactorJob{T.Sb, T.g_s, T.Ub, T.Ubk, T.ybuf, nullptr, np / 6, -1};
   T.fj[1] = FactorJob{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, -1};
   T.xsol = p->d_xsol.p, T.join_flag = p->d_join.p, T.join_epoch = 0;
-  {  // (one number, 64 bits: the values of the first 32 switches are what atoi made of them)
+  {  // HS_DEBUG_FLAGS: the measurement switches of switches.hpp (one number, 64 bits: the values of the first 32 switches are what atoi made of them)
     const long long flags = std::getenv("HS_DEBUG_FLAGS") ? std::atoll(std::getenv("HS_DEBUG_FLAGS")) : 0;
     T.debug_flags = int(flags), T.debug_flags2 = flags > 0 ? int(flags >> 32) : 0;
   }
   {  // the reversed copy feeds the far end of a two-ended factorisation and, as the lower band, every MFMA factorisation
-    const bool la_ok = la_compute_waves(vs.bw) > 0, two_ended = la_ok && np / 6 >= 4 * vs.bw;
-    const bool need = two_ended || (HS_AB(T.debug_flags, 131072) && mfma_window_tiles(vs.bw) > 0);
+    const bool two_ended = la_kernel_fits(vs.bw) && np / 6 >= 4 * vs.bw;
+    const bool need = two_ended || (HS_AB(T, sw::factor_mfma) && mfma_window_tiles(vs.bw) > 0);
     T.Sb2 = need ? p->d_Sb2.p : nullptr, T.g2 = need ? p->d_g2.p : nullptr;
   }
   T.scale_b = p->d_scale_b.p, T.Spb = p->d_Spb.p, T.Sbb = p->d_Sbb.p, T.gb_s = p->d_gb_s.p, T.D2b = p->d_D2b.p;
@@ -963,27 +968,6 @@ int prepare(hs_problem* p) {
   T.build_stream_lg = p->fused ? build_streams_packed(vs.bw, k) : 0;
   T.ch_gmax = p->d_ch_gmax.p;
   T.rank = p->rank, T.world = p->world;
-  // HS_DEBUG_FLAGS (measurement switches only, never needed for correct operation):
-  //    1 skip the backward sweep          2 skip the rank-6 updates (timing of the panel chain alone; results are garbage)
-  //    4 one-ended pre-look-ahead factorisation kernel                16 phase timestamps of the factorisation -> hs_debug_read
-  //   32 per-workgroup timestamps of the linearise / gram kernels   1024 no side stream for the segment partials
-  //   64 two-ended factorisation on the VALU look-ahead kernel (k_band_factor_la) instead of k_band_factor_mx (bw <= 14)
-  // 2048 one-ended factorisation (no second workgroup)              8192 generalised backward sweep on the one-ended factor
-  // 131072 k_band_factor_mfma (trailing window in f64 MFMA tiles) instead of the VALU factorisation kernels
-  // 65536 single-wave register backward sweep (k_band_backward_w) instead of the four-wave LDS sweeps
-  // 262144 eliminate / sweep the decoupled block rows of leading constant control points like any other     524288 border Cholesky in LDS
-  // 128 border forward sweep behind the factorisation instead of alongside it
-  //   8 small systems (6 n_free + nb <= 256) on the one-ended band kernels + border chain + k_band_backward instead of k_dense_solve_mx
-  // 256 phase timestamps of k_assemble (profiling builds)          512 phase timestamps of k_update_visual (profiling builds)
-  //   (64 and 128 are product A/B switches: the stamps of k_assemble / k_update_visual used to share them, so that timing one of those kernels
-  //    also changed the factorisation path)
-  // 1048576 inertial branch on the main stream    2097152 banded kernels instead of k_dense_factor    4194304 k_landmark<K,4,1> instead of k_landmark_rows
-  // 8192 with a border: k_border_solve_reg instead of k_dense_solve_mx on the border Schur complement of a two-ended system
-  // 8388608 five finalisation launches for a bordered single shard    16777216 k_commit launch for small windows    33554432 one cost launch per factor type
-  // 134217728 prior / inertial candidate costs as launches of their own behind k_update_visual (single shard, fused path)
-  // 16384 border gathers / pipelined border sweep joined to the main stream by events instead of device flags (Tables::gather_epoch, sweep_epoch)
-  // 4294967296 (debug_flags2 & 1, product A/B switch) backward sweep in two phases per super-step: k_band_backward_sb instead of k_band_backward_pm
-  // 268435456 backward sweeps one block row per step    536870912 bordered systems one-ended    1073741824 no speculative linearisation at the candidate    67108864 k_commit in every iteration of a speculative solve
   T.st = p->d_state.p;
   HIP_TRY(p->batch.flush(s));  // (the staging arena outlives this call: no host synchronisation)
   p->dirty = false, p->changed = 0;

@@ -66,7 +66,7 @@ HSD int sb_inverse_lds(const Tables& T, const BackJob& J, int job, int s, double
   double* Tm = lds + 2 * kSbN * LD;
   const int ncb = 6 * T.bw, n_own = 6 * J.n_rows, r0 = kSbN * s;
   const int nr = min(kSbN, n_own - r0);
-  const bool iprof = prof_enabled(T.debug_flags, 16) && l == 0 && job == 0 && s == sb_count(J.n_rows) - 1;  // -> xpart[8 * 260 ..]
+  const bool iprof = prof_enabled(T.debug_flags, sw::stamp_factor) && l == 0 && job == 0 && s == sb_count(J.n_rows) - 1;  // -> xpart[8 * 260 ..]
   long long* ilog = reinterpret_cast<long long*>(T.xpart) + 8 * 260;
   if (iprof) ilog[0] = wall_clock64();
   {  // every load first (nine + five per lane), then the stores: a load -> store loop pays the memory latency once per trip
@@ -132,7 +132,7 @@ HSD void sb_inverse(const Tables& T, const BackJob& J, int job, int s, double* l
   constexpr int LD = kSbN + 1;
   const int nr = sb_inverse_lds(T, J, job, s, lds);
   const double* V = lds + kSbN * LD;
-  const bool iprof = prof_enabled(T.debug_flags, 16) && l == 0 && job == 0 && s == sb_count(J.n_rows) - 1;
+  const bool iprof = prof_enabled(T.debug_flags, sw::stamp_factor) && l == 0 && job == 0 && s == sb_count(J.n_rows) - 1;
   long long* ilog = reinterpret_cast<long long*>(T.xpart) + 8 * 260;
   double* dst = const_cast<double*>(J.Vb) + size_t(s) * (kSbN * kSbN);
   for (int e = l; e < kSbN * kSbN; e += 64) {
@@ -169,7 +169,7 @@ HSD void sb_sweep(const Tables& T, const BackJob& j0, const BackJob& j1, const i
   const BackJob J = job == 0 ? j0 : j1;
   constexpr int nthr = kCholThreads;
   const int bw = T.bw, ncb = 6 * bw, np = T.np;
-  const bool cprof = prof_enabled(T.debug_flags, 16) && tid == 0;  // coarse phases -> xpart[8 (230 + 10 block) + ..] (tools/chol_phase_timing.py)
+  const bool cprof = prof_enabled(T.debug_flags, sw::stamp_factor) && tid == 0;  // coarse phases -> xpart[8 (230 + 10 block) + ..] (tools/chol_phase_timing.py)
   long long* clog = reinterpret_cast<long long*>(T.xpart) + 8 * (230 + 10 * job);
   if (cprof) clog[0] = wall_clock64();
   const int n_own = 6 * J.n_rows, n_all = 6 * (J.n_rows + J.given);
@@ -478,7 +478,7 @@ HSD void sb_stacked(const Tables& T, const BackJob& J, int job, int s, double* l
   const int tid = threadIdx.x, l = tid & 63;
   constexpr int LD = kSbN + 1;
   const int ncb = 6 * T.bw, n_own = 6 * J.n_rows, r0 = kSbN * s, n_above = 6 * (T.bw - 1);
-  const bool iprof = prof_enabled(T.debug_flags, 16) && tid == 0 && job == 0 && s == sb_count(J.n_rows) - 1;  // -> xpart[8 * 260 ..]
+  const bool iprof = prof_enabled(T.debug_flags, sw::stamp_factor) && tid == 0 && job == 0 && s == sb_count(J.n_rows) - 1;  // -> xpart[8 * 260 ..]
   long long* ilog = reinterpret_cast<long long*>(T.xpart) + 8 * 260;
   double* dst = const_cast<double*>(J.Mb) + sb_stack_doubles(T.bw) * size_t(s);
   const double* V = lds + kSbN * LD;
@@ -531,7 +531,7 @@ HSD void sb_sweep_pm(const Tables& T, const BackJob& j0, const BackJob& j1, cons
   const BackJob J = job == 0 ? j0 : j1;
   constexpr int nthr = kCholThreads;
   const int bw = T.bw, ncb = 6 * bw, np = T.np;
-  const bool cprof = prof_enabled(T.debug_flags, 16) && tid == 0;  // coarse phases -> xpart[8 (230 + 10 block) + ..] (tools/chol_phase_timing.py)
+  const bool cprof = prof_enabled(T.debug_flags, sw::stamp_factor) && tid == 0;  // coarse phases -> xpart[8 (230 + 10 block) + ..] (tools/chol_phase_timing.py)
   long long* clog = reinterpret_cast<long long*>(T.xpart) + 8 * (230 + 10 * job);
   if (cprof) clog[0] = wall_clock64();
   const int n_own = 6 * J.n_rows, n_all = 6 * (J.n_rows + J.given);

@@ -842,7 +842,7 @@ __global__ void __launch_bounds__(kBlock) k_border_solve_reg(Tables T) {
   // updated column j + 1 itself (c1'[i] = c1[i] - l_ij c0[j + 1], the very FMA its owners would have done) and applies both updates.
   // The chain per column is publish -> barrier -> 1 / d -> operands -> update (0.63 us at 57 unknowns, 1.04 us at 99): half the barriers.
   int j = 0;
-  const bool bprof = prof_enabled(T.debug_flags, 16) && tid == 0;  // phase stamps -> xpart[8 (700 + j / 2) + ..] (tools/border_phase_timing.py)
+  const bool bprof = prof_enabled(T.debug_flags, sw::stamp_factor) && tid == 0;  // phase stamps -> xpart[8 (700 + j / 2) + ..] (tools/border_phase_timing.py)
   long long* blog = reinterpret_cast<long long*>(T.xpart) + 8 * 700;
   // The loop over the pairs is split by the 16-column block Q the pair lies in (compile time): its owners publish a[.][Q] without a
   // run-time choice of the register column — as a chain of `if (q == j >> 4)` around the stores that choice cost 14 branches per pair,

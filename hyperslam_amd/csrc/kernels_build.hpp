@@ -251,7 +251,7 @@ __global__ void __launch_bounds__(kBlock, 2) k_build_visual(Tables T, int R, int
   int* lane_tile = pos + nseg * (Lmax + 1) + (bw + 3) / 4;  // phase 3 (at most 64 band tiles): rb | d << 8 | log2(streams) << 12 of the lane's tile, -1: idle
 
   // phase timestamps (profiling builds only, HS_DEBUG_FLAGS 32; tools/build_phase_timing.py): lane 0 of every wave of the first 1024 chunks
-  const bool bprof = prof_enabled(T.debug_flags, 32) && lane == 0 && w < 1023;  // (row 1023: the decision workgroup of a fold-mode launch, pack_decision_body)
+  const bool bprof = prof_enabled(T.debug_flags, sw::stamp_build) && lane == 0 && w < 1023;  // (row 1023: the decision workgroup of a fold-mode launch, pack_decision_body)
   long long* blog = reinterpret_cast<long long*>(T.xpart) + 48 * 1024 + 64 * w + 16 * wave;
 #define HS_BSTAMP(i) \
   if (bprof) blog[i] = wall_clock64()
@@ -920,7 +920,7 @@ HSD bool update_visual_workgroup(const Tables& T, int R, int Lmax, int n_vis_par
     return true;
   }
   // ---- chunk w ----
-  const bool uprof = prof_enabled(T.debug_flags, 512) && tid == 0 && w < 1024;  // phase stamps (profiling builds; tools/update_phase_timing.py)
+  const bool uprof = prof_enabled(T.debug_flags, sw::stamp_update) && tid == 0 && w < 1024;  // phase stamps (profiling builds; tools/update_phase_timing.py)
   long long* ulog = reinterpret_cast<long long*>(T.xpart) + 192 * 1024 + 16 * w;
   if (uprof) ulog[0] = wall_clock64();
   const int4 d0 = *reinterpret_cast<const int4*>(T.ch_desc + 8 * w);

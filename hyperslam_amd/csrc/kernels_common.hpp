@@ -3,19 +3,21 @@
 #include <type_traits>
 #include "factors.hpp"
 #include "device_primitives.hpp"
+#include "switches.hpp"
 
 namespace hs {
 
 constexpr int kBlock = 256;
 
-/// Phase-timestamp hooks (wall_clock64 writes behind HS_DEBUG_FLAGS 16 / 32, read by tools/*_phase_timing.py) exist only in
+/// Phase-timestamp hooks (wall_clock64 writes behind the stamp_* switches of switches.hpp, read by tools/*_phase_timing.py) exist only in
 /// profiling builds: with the default HS_PROFILE_HOOKS = 0 every `prof` predicate below is a compile-time false and the product
 /// kernels carry no timing code.
 #ifndef HS_PROFILE_HOOKS
 #define HS_PROFILE_HOOKS 0
 #endif
 constexpr int kDenseLd = 256;  // leading dimension of the dense copy of a small reduced system (Tables::dense, kernels_dense_mx.hpp)
-HSD bool prof_enabled(int debug_flags, int bit) { return HS_PROFILE_HOOKS && (debug_flags & bit); }
+template <unsigned long long Mask>
+HSD bool prof_enabled(int debug_flags, Switch<Mask> s) { return HS_PROFILE_HOOKS && (debug_flags & s.low()); }
 
 constexpr int kGatherFlag = 4 + 2 * 512 + 512 + 4 * kProgressStride;  // word of T.join_flag behind every other use (kBfFlagBase + 512 + 4 kProgressStride)
 

@@ -380,7 +380,7 @@ __global__ void __launch_bounds__(kDxThreads) k_dense_solve_mx(Tables T, int f0,
   const int n_pose = T.np - 6 * f0, n_dense = n_pose + T.nb, nt = (n_dense + 1 + 15) / 16, n_pad = 16 * nt;
   double* xv = smem + kDxOffX;
   double* wk = smem + kDxOffW;
-  const bool prof = prof_enabled(T.debug_flags, 16) && tid == 0;  // phase stamps (profiling builds, tools/dense_mx_phase_timing.py)
+  const bool prof = prof_enabled(T.debug_flags, sw::stamp_factor) && tid == 0;  // phase stamps (profiling builds, tools/dense_mx_phase_timing.py)
   long long* tlog = reinterpret_cast<long long*>(T.xpart) + 8 * 300;
   if (prof) tlog[-1] = wall_clock64();
   // wave (a, b) = (w / 4, w mod 4): SIMD w mod 4 holds one wave of each row class, all of column class b

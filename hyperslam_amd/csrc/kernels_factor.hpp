@@ -143,7 +143,7 @@ __global__ void __launch_bounds__(kCholThreads + kCholIo) k_band_factor(Tables T
     }
   };
   lds_barrier();  // initial window loaded / staged
-  const bool prof = prof_enabled(T.debug_flags, 16) && tid == 0;
+  const bool prof = prof_enabled(T.debug_flags, sw::stamp_factor) && tid == 0;
   long long* tlog = reinterpret_cast<long long*>(T.xpart);
 
 #define UIDX(a, c) ((a) * 6 - (a) * ((a)-1) / 2 + ((c) - (a)))
@@ -246,7 +246,7 @@ __global__ void __launch_bounds__(kCholThreads + kCholIo) k_band_factor(Tables T
     for (int m = 0; m < TPT; ++m) {
       int j = t_slot[m] - si;
       if (j < 0) j += bw;
-      if (!t_ok[m] || j == 0 || j + t_kk[m] > bw - 1 || (T.debug_flags & 2)) continue;
+      if (!t_ok[m] || j == 0 || j + t_kk[m] > bw - 1 || (T.debug_flags & sw::skip_rank6.low())) continue;
       const int ca = 6 * j, cb = 6 * (j + t_kk[m]);
       // the right-hand side rides along in every lane (only the lanes with kk = 0 use theirs): as a branch around its loads and FMAs it
       // drained the LDS queue once per row of X (see k_band_factor_la)
@@ -483,7 +483,7 @@ __global__ void __launch_bounds__(la_threads(NCW)) k_band_factor_la(Tables T) {
         tput(tb, rowbuf + (i & 1) * 6 * ld, i + 2);
         fetch(vb, i + 5 + bw);
         tfetch(tb, i + 4);
-        if (prof_enabled(T.debug_flags, 16) && l == 0) reinterpret_cast<long long*>(T.xpart)[8 * i + 7] = wall_clock64();
+        if (prof_enabled(T.debug_flags, sw::stamp_factor) && l == 0) reinterpret_cast<long long*>(T.xpart)[8 * i + 7] = wall_clock64();
         lds_barrier();
         junction_io(i);
         if (i + 1 < n_steps) {
@@ -537,7 +537,7 @@ __global__ void __launch_bounds__(la_threads(NCW)) k_band_factor_la(Tables T) {
               if (a <= c) J.Ubk[size_t(i) * 24 + (a * 6 - a * (a - 1) / 2 + (c - a))] = w[a];
           }
         }
-        if (prof_enabled(T.debug_flags, 16) && l == 0) reinterpret_cast<long long*>(T.xpart)[8 * i + 6] = wall_clock64();
+        if (prof_enabled(T.debug_flags, sw::stamp_factor) && l == 0) reinterpret_cast<long long*>(T.xpart)[8 * i + 6] = wall_clock64();
         lds_barrier();
         if (m_at >= 0 && i + 1 == m_at) {
           junction_wait();
@@ -555,7 +555,7 @@ __global__ void __launch_bounds__(la_threads(NCW)) k_band_factor_la(Tables T) {
 
   if (wave == 3) {  // ================================ panel wave (alone on SIMD 3) ================================
 #define UIDX(a, c) ((a) * 6 - (a) * ((a)-1) / 2 + ((c) - (a)))
-    const bool pprof = prof_enabled(T.debug_flags, 16) && l == 0;
+    const bool pprof = prof_enabled(T.debug_flags, sw::stamp_factor) && l == 0;
     long long* plog = reinterpret_cast<long long*>(T.xpart);
     // column bookkeeping of this lane (loop invariant): c = l + 64 m; lanes past the row write to the pad column ncb + 1
     int c_rd[PC], c_src[PC], c_wr[PC];
@@ -757,7 +757,7 @@ __global__ void __launch_bounds__(la_threads(NCW)) k_band_factor_la(Tables T) {
       rhs[m][a] = (in && t_kk[m] == 0) ? J.g_s[6 * r + a] : 0.0;
     }
   }
-  const bool cprof = prof_enabled(T.debug_flags, 16) && tid == 0;  // coarse phases of this workgroup -> tlog[8 (200 + 10 job) + ..]
+  const bool cprof = prof_enabled(T.debug_flags, sw::stamp_factor) && tid == 0;  // coarse phases of this workgroup -> tlog[8 (200 + 10 job) + ..]
   long long* clog = reinterpret_cast<long long*>(T.xpart) + 8 * (200 + 10 * blockIdx.x);
   if (cprof) clog[0] = wall_clock64();  // tiles requested
   wait_vmem();
@@ -765,8 +765,8 @@ __global__ void __launch_bounds__(la_threads(NCW)) k_band_factor_la(Tables T) {
   lds_barrier();  // init
   lds_barrier();  // prologue: X_0 complete
   if (cprof) clog[2] = wall_clock64();
-  const bool prof = prof_enabled(T.debug_flags, 16) && tid == 0 && blockIdx.x == 0;
-  const bool prof12 = prof_enabled(T.debug_flags, 16) && (tid == 64 || tid == 128) && blockIdx.x == 0;  // compute waves 1, 2 -> tlog[8 (512 + i) + 2 wave ..]
+  const bool prof = prof_enabled(T.debug_flags, sw::stamp_factor) && tid == 0 && blockIdx.x == 0;
+  const bool prof12 = prof_enabled(T.debug_flags, sw::stamp_factor) && (tid == 64 || tid == 128) && blockIdx.x == 0;  // compute waves 1, 2 -> tlog[8 (512 + i) + 2 wave ..]
   long long* tlog = reinterpret_cast<long long*>(T.xpart);
   for (int i = 0; i < n_steps; ++i) {
     if (prof) tlog[8 * i + 0] = wall_clock64();
@@ -791,7 +791,7 @@ __global__ void __launch_bounds__(la_threads(NCW)) k_band_factor_la(Tables T) {
         t_refill[m] = false;
       }
       if (!t_ok[m] || j < 2 || j > bw - 1) continue;
-      if (j + t_kk[m] <= bw - 1 && !(T.debug_flags & 2)) {  // rank-6 update  S_(i+j),kk -= X_j' X_(j+kk)
+      if (j + t_kk[m] <= bw - 1 && !(T.debug_flags & sw::skip_rank6.low())) {  // rank-6 update  S_(i+j),kk -= X_j' X_(j+kk)
         const int ca = 6 * j, cb = 6 * (j + t_kk[m]);
         // The right-hand side rides along as a seventh column in EVERY lane (only the lanes with kk = 0 ever use theirs): as a branch
         // around six loads and FMAs per row of X it cost a full drain of the LDS queue per row (s_waitcnt lgkmcnt(0) inside the
@@ -1129,7 +1129,7 @@ __global__ void __launch_bounds__(kCholThreads) k_band_backward(Tables T, int j_
   double* xout = xs + T.np;  // np : final x
   __shared__ double Wl[2][24];
   for (int rho = tid; rho < T.np; rho += nthr) xs[rho] = T.ybuf[rho], xout[rho] = 0.0;
-  if (T.debug_flags & 1) return;  // timing experiments only (HS_DEBUG_FLAGS)
+  if (T.debug_flags & sw::skip_backward.low()) return;  // timing experiments only (HS_DEBUG_FLAGS)
 
   // ---- backward solve U x = y, column oriented: once x_j is final every pending row above subtracts U[rho][x_j] ----
   // thread t owns pending row rho = 6 j - 1 - t of step j; its six U entries (contiguous in the band row) and U_jj^-1
@@ -1267,7 +1267,7 @@ __global__ void __launch_bounds__(kDenseThreads) k_dense_factor(Tables T, int n_
   // HS_DEBUG_FLAGS 16: phase timestamps (100 MHz clock) -> hs_debug_read, tools/dense_phase_timing.py. Per block row k (8 slots):
   // [0] barrier after A, [1] barrier after B (thread 0); [2] row owner (k, k + 1): solve done, [3] stores issued; diagonal owner
   // (k + 1, k + 1): [4] update done, [5] factorised and published
-  const bool prof = prof_enabled(T.debug_flags, 16);
+  const bool prof = prof_enabled(T.debug_flags, sw::stamp_factor);
   long long* tlog = reinterpret_cast<long long*>(T.xpart) + 8 * 300;
   if (prof && tid == 0) tlog[-1] = wall_clock64();
   // ---- static tile ownership: slot t = tid + 512 m -> (i, j), row major over rows i with columns j = i .. min(i + bw, n) - 1 and

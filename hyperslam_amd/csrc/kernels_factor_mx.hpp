@@ -232,7 +232,7 @@ HSD void mx_tiles_wave(const Tables& T, const MfmaJob& J, double* smem, int l, i
   double* xring = smem + kMxX;
   double* rowbuf = smem + kMxR;
   const double* stage = smem + kMxS;
-  const bool prof = prof_enabled(T.debug_flags, 16) && l == 0 && blockIdx.x == 0;
+  const bool prof = prof_enabled(T.debug_flags, sw::stamp_factor) && l == 0 && blockIdx.x == 0;
   long long* tlog = reinterpret_cast<long long*>(T.xpart);
   mx_f64x4 acc[TW];
   // prologue: the pairs among block rows 2 .. 15, ring position = matrix index (block rows 0 and 1 start in rowbuf)
@@ -475,7 +475,7 @@ __global__ void __launch_bounds__(kMxThreads) k_band_factor_mx(Tables T) {
   double* rowbuf = smem + kMxR;
   double* stage = smem + kMxS;
   double* dinv = smem + kMxD;  // 2 x 8: 1 / diag(U_ii) of block row i in dinv[i & 1] (panel -> storer)
-  const bool prof = prof_enabled(T.debug_flags, 16) && l == 0 && blockIdx.x == 0;  // phase timestamps -> hs_debug_read (tools/mx_phase_timing.py)
+  const bool prof = prof_enabled(T.debug_flags, sw::stamp_factor) && l == 0 && blockIdx.x == 0;  // phase timestamps -> hs_debug_read (tools/mx_phase_timing.py)
   long long* tlog = reinterpret_cast<long long*>(T.xpart);
   long long* plog = tlog + 8 * 1024;
   __shared__ int fail;
@@ -711,7 +711,7 @@ __global__ void __launch_bounds__(kMxThreads) k_band_factor_mx(Tables T) {
     }
   } else {  // ================================ panel waves (hw 2 and 3: each alone on its SIMD) ================================
     const bool chain = hw == 3;  // wave 3: the upper half of the ring, the right-hand side, 1 / diag for the storer, `fail`
-    const bool cprof = prof_enabled(T.debug_flags, 16) && chain && l == 0;  // coarse phases of this job -> tlog[8 (590 + 4 job) + ..]
+    const bool cprof = prof_enabled(T.debug_flags, sw::stamp_factor) && chain && l == 0;  // coarse phases of this job -> tlog[8 (590 + 4 job) + ..]
     long long* clog = tlog + 8 * (590 + 4 * blockIdx.x);
     if (cprof) clog[0] = wall_clock64();
     MxLane L;
@@ -799,7 +799,7 @@ __global__ void __launch_bounds__(kMxThreads) k_band_factor_mx(Tables T) {
     if (tid == 0) {
       __threadfence();
       __hip_atomic_store(T.join_flag, T.join_epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      if (prof_enabled(T.debug_flags, 16)) tlog[8 * (590 + 4 * blockIdx.x) + 7] = wall_clock64();  // window handed over
+      if (prof_enabled(T.debug_flags, sw::stamp_factor)) tlog[8 * (590 + 4 * blockIdx.x) + 7] = wall_clock64();  // window handed over
     }
   }
   // Iteration bookkeeping of a directly assembled system (Tables::bookkeep, factor_bookkeep): a wave of the FAR end, behind its hand-over —

@@ -249,7 +249,7 @@ HSD void seg_gram_body(const Tables& T, const int bid) {
   const int first = T.sw_seg[bid], sp = bid - T.sw_ptr[first], nsp = T.sw_ptr[first + 1] - T.sw_ptr[first];
   const int tid = threadIdx.x;
   const int stream = tid / TPS, tb = tid % TPS, rg = tb / CG, cg = tb % CG;
-  const bool sprof = prof_enabled(T.debug_flags, 32) && tid == 0 && sp == 0 && first < 128;
+  const bool sprof = prof_enabled(T.debug_flags, sw::stamp_build) && tid == 0 && sp == 0 && first < 128;
   long long* slog = reinterpret_cast<long long*>(T.xpart) + 8 * 1024 + 8 * first;
   if (sprof) slog[0] = wall_clock64();
   // a tile is needed if some column block >= the row block (upper block triangle); column group 0 also carries J'r
@@ -386,7 +386,7 @@ HSD void group_gram_body(const Tables& T, const int batch, const int bid) {
 #pragma unroll
     for (int e = 0; e < 6; ++e) qacc[m][e] = 0.0;
   }
-  const bool gprof = prof_enabled(T.debug_flags, 32) && tid == 0 && sp == 0 && cf < 128;
+  const bool gprof = prof_enabled(T.debug_flags, sw::stamp_build) && tid == 0 && sp == 0 && cf < 128;
   long long* glog = reinterpret_cast<long long*>(T.xpart) + 8 * cf;
   if (gprof) glog[0] = wall_clock64();
   const int dl0 = T.cf_ptr[cf], dl1 = T.cf_ptr[cf + 1];
@@ -525,7 +525,7 @@ HSD void assemble_body(const Tables& T, int direct) {
   __shared__ double part[3][THREADS];
   __shared__ double gpair[2];
   // phase timestamps (profiling builds, HS_DEBUG_FLAGS 64; tools/assemble_phase_timing.py): lane 0 of every workgroup
-  const bool aprof = prof_enabled(T.debug_flags, 256) && threadIdx.x == 0;
+  const bool aprof = prof_enabled(T.debug_flags, sw::stamp_assemble) && threadIdx.x == 0;
   long long* alog = reinterpret_cast<long long*>(T.xpart) + 128 * 1024 + 8 * (blockIdx.y * gridDim.x + blockIdx.x);
   if (aprof) alog[0] = wall_clock64();
   if (T.st->done) return;

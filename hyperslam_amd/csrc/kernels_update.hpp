@@ -227,7 +227,7 @@ HSD void pack_decision_body(const Tables& T, const int decide_here, double* red 
   DevState* st = T.st;
   const int done_at_entry = st->done;  // (requested with the partials below, looked at behind them: one memory round trip, not two)
   // phase stamps of the decision workgroup of a fold-mode build (profiling builds, HS_DEBUG_FLAGS 32; tools/fold_phase_timing.py)
-  const bool dprof = prof_enabled(T.debug_flags, 32) && publish && threadIdx.x == 0;
+  const bool dprof = prof_enabled(T.debug_flags, sw::stamp_build) && publish && threadIdx.x == 0;
   long long* dlog = reinterpret_cast<long long*>(T.xpart) + 48 * 1024 + 64 * 1023;
   if (dprof) dlog[0] = wall_clock64();
   DecideIn din = {};

@@ -322,9 +322,9 @@ int hs_set_stage_timing(hs_problem* p, int enabled);
  * the size asked for, followed by a known pattern, and hs_solve / hs_cost / hs_reduced_system / hs_linearize check the patterns of all of them
  * before they return (HS_ERR_DEVICE with the table's size if a kernel wrote past the end of one). Slow; meant for test suites. */
 int hs_set_guard(int enabled);
-/* Measurement switches: HS_DEBUG_FLAGS in the environment, a sum of bits read when the tables of a handle are prepared (the list is in
- * csrc/host_tables.hpp; never needed for correct operation, most of them exist in profiling builds only). One of the product's:
- *   4294967296  backward sweep of the band solve with two phases per super-step (k_band_backward_sb, the sweep up to round 6) instead of one
+/* Measurement switches: HS_DEBUG_FLAGS in the environment, a sum of bits read when the tables of a handle are prepared (the list, one named line per
+ * switch, is csrc/switches.hpp; never needed for correct operation, most of them exist in profiling builds only). One of the product's:
+ *   4294967296  (backward_sb) backward sweep of the band solve with two phases per super-step (k_band_backward_sb, the sweep up to round 6) instead of one
  *               phase on premultiplied blocks (k_band_backward_pm); same results up to rounding. */
 int hs_set_allreduce(hs_problem* p, hs_allreduce_fn fn, void* user);
 /* RCCL on the data path without a host hook: rank 0 obtains a 128-byte unique id (ncclGetUniqueId), the caller distributes it

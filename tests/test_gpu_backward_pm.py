@@ -1,5 +1,5 @@
 """The backward sweep with one phase per super-step on premultiplied blocks (k_band_backward_pm, the default) against the two-phase sweep
-it replaces (k_band_backward_sb behind the product switch HS_DEBUG_FLAGS=4294967296) and against the oracle, on windows whose reduced
+it replaces (k_band_backward_sb behind the product switch backward_sb, HS_DEBUG_FLAGS=4294967296) and against the oracle, on windows whose reduced
 system is factored from both ends: configs[1]'s band at half its length, a short band, and a bordered (stereo-inertial) one.
 Tolerances: tests/test_gpu_parity.py::test_solve_trajectory's (the bar of the HIP path against the oracle); the two sweeps differ in rounding
 only — (U Winv) y instead of U (Winv y) — so they are held to the same bar against each other."""
@@ -7,11 +7,11 @@ import numpy as np
 import pytest
 
 import hyperslam_amd as ha
-from hyperslam_amd import synthetic
+from hyperslam_amd import switches, synthetic
 
 pytestmark = pytest.mark.gpu
 
-TWO_PHASE = str(4294967296)
+TWO_PHASE = switches.flags("backward_sb")
 
 
 def rel(a, b):

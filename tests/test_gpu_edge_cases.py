@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import hyperslam_amd as ha
-from hyperslam_amd import synthetic
+from hyperslam_amd import switches, synthetic
 from util import rel
 
 pytestmark = pytest.mark.gpu
@@ -238,11 +238,11 @@ def test_narrow_bands_from_both_ends(span, hip, oracle):
 
 @pytest.mark.parametrize("bw,imu", [(10, False), (14, False), (16, False), (14, True), (16, True)])
 def test_mfma_and_valu_factorisations_agree(bw, imu, hip, monkeypatch):
-    """The two two-ended factorisations of the library — k_band_factor_mx (default) and k_band_factor_la (measurement switch 64) — on the same
+    """The two two-ended factorisations of the library — k_band_factor_mx (default) and k_band_factor_la (measurement switch factor_la, 64) — on the same
     window: same accept / reject sequence, final state to 1e-9 (two summation orders of one Cholesky factorisation)."""
     w = window_with_band(4, bw, n_cp=72, imu=imu)
     runs = []
-    for flags in ("0", "64"):
+    for flags in ("0", switches.flags("factor_la")):
         monkeypatch.setenv("HS_DEBUG_FLAGS", flags)
         with ha.Problem(w, lib=hip) as g:
             s = g.solve(5)
@@ -272,7 +272,7 @@ def test_long_window(hip, monkeypatch):
     factorisation / sweep must agree; windows beyond the LDS budget (> 1024 control points) are rejected with a message."""
     w = synthetic.small_visual(order=4, n_cp=900, n_landmarks=2700, obs_pairs=2, seed=43, with_priors=900)
     sols = []
-    for flags in ("0", "2048"):  # 2048: one-ended (measurement switch of the library)
+    for flags in ("0", switches.flags("one_ended")):  # 2048: one-ended (measurement switch of the library)
         monkeypatch.setenv("HS_DEBUG_FLAGS", flags)
         with ha.Problem(w, lib=hip) as g:
             s = g.solve(3)
@@ -413,14 +413,14 @@ def test_huber_at_the_threshold(bearing, hip, oracle):
 @pytest.mark.parametrize("order,bw,n_cp,imu", [(4, 15, 30, False), (4, 16, 24, False), (4, 22, 30, False), (4, 30, 36, True), (6, 33, 41, True), (4, 33, 47, False)])
 def test_short_windows_with_window_wide_bands(order, bw, n_cp, imu, hip, oracle, monkeypatch):
     """The shape of the sliding-window replay: a few dozen free control points and tracks as long as the window. These systems take the
-    register-resident k_dense_factor (n - frozen <= 2 bw, bw > 14, <= 1024 tile slots); the banded kernels (HS_DEBUG_FLAGS=2097152) must
+    register-resident k_dense_factor (n - frozen <= 2 bw, bw > 14, <= 1024 tile slots); the banded kernels (switch no_dense_factor, 2097152) must
     give the same step."""
     w = window_with_band(order, bw, n_cp=n_cp, imu=imu)
     compare(w, hip, oracle)
     with ha.Problem(w, lib=hip) as g:
         s1 = g.solve(3)
         cp1 = g.control_points()
-    monkeypatch.setenv("HS_DEBUG_FLAGS", "2097152")
+    monkeypatch.setenv("HS_DEBUG_FLAGS", switches.flags("no_dense_factor"))
     with ha.Problem(w, lib=hip) as g:
         s2 = g.solve(3)
         cp2 = g.control_points()
@@ -438,8 +438,8 @@ def test_short_windows_with_window_wide_bands(order, bw, n_cp, imu, hip, oracle,
     assert abs(s1["final_cost"] - s3["final_cost"]) <= 1e-9 * s3["final_cost"]
 
 
-@pytest.mark.parametrize("flags,what", [(4194304, "k_landmark<K,4,1> instead of k_landmark_rows"), (8388608, "five finalisation launches instead of one"),
-                                         (16777216, "k_commit launch instead of the inline copy"), (262144, "no frozen-prefix shortcuts")])
+@pytest.mark.parametrize("flags,what", [(switches.value("landmark_wave"), "k_landmark<K,4,1> instead of k_landmark_rows"), (switches.value("finalize_five"), "five finalisation launches instead of one"),
+                                         (switches.value("commit_launch"), "k_commit launch instead of the inline copy"), (switches.value("no_decouple"), "no frozen-prefix shortcuts")])
 @pytest.mark.parametrize("imu", [False, True])
 def test_replay_shape_launch_variants_agree(flags, what, imu, hip, monkeypatch):
     """The launch arrangements added for the sliding-window shape (long tracks, frozen prefix, bordered single shard, small state) against
@@ -456,7 +456,7 @@ def test_replay_shape_launch_variants_agree(flags, what, imu, hip, monkeypatch):
     monkeypatch.setenv("HS_DEBUG_FLAGS", "0")
     (s0, cp0, lm0), (s1, cp1, lm1) = runs
     assert s0["num_iterations"] == s1["num_iterations"] and s0["num_successful_steps"] == s1["num_successful_steps"], what
-    if flags == 262144:
+    if flags == switches.value("no_decouple"):
         assert rel(cp0, cp1) < 1e-9 and rel(lm0, lm1) < 1e-9 and abs(s0["final_cost"] - s1["final_cost"]) <= 1e-9 * s1["final_cost"], what
     else:
         assert np.array_equal(cp0, cp1) and np.array_equal(lm0, lm1) and s0["final_cost"] == s1["final_cost"], what
@@ -511,7 +511,7 @@ def test_rejected_steps_on_visual_windows(seed, lm_noise, cp_noise, order, beari
     (capi.hip: speculative_solve). On both, above 4096 state scalars (the 1500-landmark cases) the accepted candidate is copied to x by the
     next iteration's k_backsub_retract instead of a k_commit launch. Starts far enough from the optimum that steps are rejected: the accept /
     reject sequence, every recorded quantity and the final state must match the oracle's (which linearises the current point at the top of
-    every iteration), the path with a commit per iteration (HS_DEBUG_FLAGS=67108864) and, on the record path, the one that does
+    every iteration), the path with a commit per iteration (switch commit_always, 67108864) and, on the record path, the one that does
     everything the oracle's way on the device (1073741824)."""
     w = perturbed_visual(seed, lm_noise, cp_noise, order, bearing, n_lm)
     n_it = 6
@@ -521,7 +521,8 @@ def test_rejected_steps_on_visual_windows(seed, lm_noise, cp_noise, order, beari
     flags_seen = [it["step_is_successful"] for it in sc["iterations"]]
     assert 0 in flags_seen[1:] and 1 in flags_seen[1:], flags_seen  # the case exercises both branches
     outs = []
-    for path, flags in (("fused", "0"), ("fused", "67108864"), ("records", "0"), ("records", "67108864"), ("records", "1073741824")):
+    for path, flags in (("fused", "0"), ("fused", switches.flags("commit_always")), ("records", "0"), ("records", switches.flags("commit_always")),
+                        ("records", switches.flags("no_speculation"))):
         monkeypatch.setenv("HS_DEBUG_FLAGS", flags)
         monkeypatch.setenv("HS_BUILD_PATH", path)
         with ha.Problem(w, lib=hip) as g:

@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 
 import hyperslam_amd as ha
-from hyperslam_amd import synthetic
+from hyperslam_amd import switches, synthetic
 from util import check_against_golden, golden_cases, golden_window, rel
 
 pytestmark = pytest.mark.gpu
@@ -66,7 +66,7 @@ def test_bordered_solve_trajectory(order, identity, grav_const, hip, oracle):
 def test_two_ended_bordered_solve(order, n_cp, hip, oracle, monkeypatch):
     """Windows long enough (n_cp >= 4 band widths) for the bordered system to be factored from both ends (k_border_forward2, the y view over
     both ends, border outputs of the two-ended backward sweep): the 5-iteration trajectory against the oracle and, bias points and gravity
-    included, against the one-ended path of the same library (A/B switch 536870912)."""
+    included, against the one-ended path of the same library (switch border_one_ended, 536870912)."""
     w = synthetic.small_inertial(order=order, n_cp=n_cp, n_landmarks=300, obs_pairs=3, n_inertial=600, seed=33)
     w.cp_constant = np.r_[np.ones(order, np.uint8), np.zeros(n_cp - order, np.uint8)]
 
@@ -85,14 +85,14 @@ def test_two_ended_bordered_solve(order, n_cp, hip, oracle, monkeypatch):
         assert ig["step_is_successful"] == ic["step_is_successful"]
         assert abs(ig["cost"] - ic["cost"]) <= 1e-6 * abs(ic["cost"]) + 1e-8 * sc["initial_cost"]
     assert rel(cpg, cpc) < 1e-6 and rel(lmg, lmc) < 1e-6 and rel(gg, gc) < 1e-6 and rel(bgg, bgc) < 1e-6 and rel(bag, bac) < 1e-6
-    monkeypatch.setenv("HS_DEBUG_FLAGS", str(536870912))  # the same window through the one-ended bordered path
+    monkeypatch.setenv("HS_DEBUG_FLAGS", switches.flags("border_one_ended"))  # the same window through the one-ended bordered path
     _, s1, cp1, lm1, g1, bg1, ba1 = run(hip)
     assert [it["step_is_successful"] for it in s1["iterations"]] == [it["step_is_successful"] for it in sg["iterations"]]
     assert rel(cpg, cp1) < 1e-8 and rel(lmg, lm1) < 1e-8 and rel(gg, g1) < 1e-8 and rel(bgg, bg1) < 1e-7 and rel(bag, ba1) < 1e-7
     # The forward sweep of the border columns runs NEXT TO the factorisation and follows its progress words (round 5: k_border_forward2 on
-    # the side stream, MfmaJob::progress); A/B switch 128 runs it behind the factorisation. Same arithmetic on the same values: every run of
+    # the side stream, MfmaJob::progress); switch sweep_behind (128) runs it behind the factorisation. Same arithmetic on the same values: every run of
     # either arrangement must give the same bits — a sweep that read a factor row before it was complete would not.
-    monkeypatch.setenv("HS_DEBUG_FLAGS", "128")
+    monkeypatch.setenv("HS_DEBUG_FLAGS", switches.flags("sweep_behind"))
     _, s2, cp2, lm2, g2, bg2, ba2 = run(hip)
     monkeypatch.setenv("HS_DEBUG_FLAGS", "0")
     for _ in range(4):

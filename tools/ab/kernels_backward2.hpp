@@ -12,7 +12,7 @@ __global__ void __launch_bounds__(kCholThreads) k_band_backward2(Tables T, BackJ
   const int tid = threadIdx.x;
   constexpr int nthr = kCholThreads;
   const int bw = T.bw, ncb = 6 * bw, np = T.np;
-  const bool cprof = prof_enabled(T.debug_flags, 16) && tid == 0;  // coarse phases -> xpart[8 (230 + 10 block) + ..] (tools/chol_phase_timing.py)
+  const bool cprof = prof_enabled(T.debug_flags, sw::stamp_factor) && tid == 0;  // coarse phases -> xpart[8 (230 + 10 block) + ..] (tools/chol_phase_timing.py)
   long long* clog = reinterpret_cast<long long*>(T.xpart) + 8 * (230 + 10 * blockIdx.x);
   if (cprof) clog[0] = wall_clock64();
   const int n_own = 6 * J.n_rows, n_all = 6 * (J.n_rows + J.given);

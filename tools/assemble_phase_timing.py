@@ -1,9 +1,10 @@
-"""Phase timestamps of k_assemble (HS_DEBUG_FLAGS=256, profiling build: tools/build_profiling_lib.sh).
+"""Phase timestamps of k_assemble (HS_DEBUG_FLAGS=256: switch stamp_assemble, profiling build: tools/build_profiling_lib.sh).
 usage (GPU box): python tools/assemble_phase_timing.py [config=1|2|3|r]   (r: the replay's steady state, window-wide band: k_assemble_wide)"""
 import os
 import sys, ctypes as C; sys.path.insert(0, ".")
 import numpy as np
-os.environ["HS_DEBUG_FLAGS"] = str(256 | int(os.environ.get("HS_DEBUG_FLAGS", "0")))
+from hyperslam_amd import switches
+switches.add_to_env("stamp_assemble")
 import hyperslam_amd as ha
 from hyperslam_amd import synthetic, _lib
 _lib.PRODUCT_LIB = os.path.join("tools", "libhyperslam_hip_prof.so")

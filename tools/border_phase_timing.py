@@ -7,7 +7,8 @@ import numpy as np
 import hyperslam_amd as ha
 from hyperslam_amd import synthetic, _lib
 _lib.PRODUCT_LIB = os.path.join("tools", "libhyperslam_hip_prof.so")
-os.environ.setdefault("HS_DEBUG_FLAGS", "16")
+from hyperslam_amd import switches
+os.environ.setdefault("HS_DEBUG_FLAGS", switches.flags("stamp_factor"))
 w = synthetic.config2()
 p = ha.Problem(w); p.snapshot()
 for i in range(2): p.restore(); s = p.solve(1)

@@ -1,9 +1,10 @@
-"""Phase timestamps of k_build_visual (HS_DEBUG_FLAGS=32, profiling build: tools/build_profiling_lib.sh).
+"""Phase timestamps of k_build_visual (HS_DEBUG_FLAGS=32: switch stamp_build, profiling build: tools/build_profiling_lib.sh).
 usage (GPU box): python tools/build_phase_timing.py [config=1|2|3|r]"""
 import os
 import sys, ctypes as C; sys.path.insert(0, ".")
 import numpy as np
-os.environ["HS_DEBUG_FLAGS"] = str(32 | int(os.environ.get("HS_DEBUG_FLAGS", "0")))
+from hyperslam_amd import switches
+switches.add_to_env("stamp_build")
 import hyperslam_amd as ha
 from hyperslam_amd import synthetic, _lib
 _lib.PRODUCT_LIB = os.path.join("tools", "libhyperslam_hip_prof.so")

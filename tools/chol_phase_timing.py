@@ -5,7 +5,8 @@ os.environ.setdefault("HS_STAGE_TIMING", "1")
 import hyperslam_amd as ha
 from hyperslam_amd import synthetic, _lib
 _lib.PRODUCT_LIB = os.path.join("tools", "libhyperslam_hip_prof.so")  # profiling build (tools/build_profiling_lib.sh): the product library has no timing hooks
-os.environ["HS_DEBUG_FLAGS"] = str(16 | int(os.environ.get("HS_DEBUG_FLAGS", "0")))
+from hyperslam_amd import switches
+switches.add_to_env("stamp_factor")
 w=getattr(synthetic, "config" + (sys.argv[1] if len(sys.argv) > 1 else "1"))()  # usage: python tools/chol_phase_timing.py [config=1]
 p=ha.Problem(w); p.snapshot()
 for i in range(2): p.restore(); s=p.solve(1)
@@ -42,11 +43,11 @@ for job in (0, 1):
 # both write the same stamps. Super-steps per block as launch_factor splits the system (block 1: + phase A, the near factor's top super-blocks).
 flags = int(os.environ["HS_DEBUG_FLAGS"])
 bw, n_blk = _lib.load().band_blocks(p.h), w.n_cp
-mx = 3 <= bw <= 16 and not flags & 64
+mx = 3 <= bw <= 16 and not flags & switches.value("factor_la")
 m = min((n_blk - (bw - 1)) // 2 + (2 if mx else 3), n_blk - 2 * (bw - 1)); mB = n_blk - (bw - 1) - m
 steps = [-(-(m + bw - 1) // 4), -(-mB // 4)]
 phase_a = steps[0] - m // 4
-print("backward sweep:", "k_band_backward_sb (two phases per super-step)" if flags & 4294967296 else "k_band_backward_pm (one phase per super-step)",
+print("backward sweep:", "k_band_backward_sb (two phases per super-step)" if flags & switches.value("backward_sb") else "k_band_backward_pm (one phase per super-step)",
       " bw", bw, " block rows near / far", m + bw - 1, mB, " super-steps", steps, " phase A steps of block 1", phase_a)
 for blk in (0, 1):
     c = buf[8 * (230 + 10 * blk): 8 * (230 + 10 * blk) + 8]

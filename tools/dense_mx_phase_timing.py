@@ -1,9 +1,10 @@
 """Phase timestamps of k_dense_solve_mx (kernels_dense_mx.hpp) on a replay-shaped window: n free block rows with window-wide bands, with or
-without an IMU (border unknowns). Profiling build (tools/build_profiling_lib.sh), HS_DEBUG_FLAGS=16; wall_clock64 ticks are 10 ns.
+without an IMU (border unknowns). Profiling build (tools/build_profiling_lib.sh), HS_DEBUG_FLAGS=16, switch stamp_factor; wall_clock64 ticks are 10 ns.
 usage (GPU box): python tools/dense_mx_phase_timing.py [n_free=33] [imu=0]"""
 import os, sys, ctypes as C
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
-os.environ["HS_DEBUG_FLAGS"] = str(16 | int(os.environ.get("HS_DEBUG_FLAGS", "0")))
+from hyperslam_amd import switches
+switches.add_to_env("stamp_factor")
 os.environ.setdefault("HS_STAGE_TIMING", "1")
 import numpy as np
 import hyperslam_amd as ha

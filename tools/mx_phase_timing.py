@@ -1,6 +1,7 @@
-"""Phase timestamps of k_band_factor_mx (profiling build, HS_DEBUG_FLAGS = 16, 100 MHz clock): python tools/mx_phase_timing.py [config]"""
+"""Phase timestamps of k_band_factor_mx (profiling build, HS_DEBUG_FLAGS = 16: switch stamp_factor, 100 MHz clock): python tools/mx_phase_timing.py [config]"""
 import os, sys, ctypes as C; sys.path.insert(0, ".")
-os.environ["HS_DEBUG_FLAGS"] = str(16 | int(os.environ.get("HS_DEBUG_FLAGS", "0")))
+from hyperslam_amd import switches
+switches.add_to_env("stamp_factor")
 import numpy as np
 os.environ.setdefault("HS_STAGE_TIMING", "1")
 import hyperslam_amd as ha

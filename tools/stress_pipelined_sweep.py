@@ -1,5 +1,5 @@
 """Stress of the pipelined border sweep (k_border_forward2 next to k_band_factor_mx): N solves of a bordered window in the
-default arrangement against ONE solve with the sweep behind the factorisation (HS_DEBUG_FLAGS=128) — every output must have the same bits.
+default arrangement against ONE solve with the sweep behind the factorisation (switch sweep_behind, HS_DEBUG_FLAGS=128) — every output must have the same bits.
 usage (GPU box): python tools/stress_pipelined_sweep.py [repeats=40]"""
 import os
 import subprocess
@@ -34,12 +34,14 @@ if __name__ == "__main__":
         np.save(sys.argv[4], np.array([np.frombuffer(r.tobytes(), np.uint64).sum(dtype=np.uint64) for r in res], np.uint64))  # checksum of the bits of every solve
         sys.exit(0)
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 40
+    from hyperslam_amd import switches
+    behind = switches.flags("sweep_behind")
     sums = {}
-    for flags, n in (("128", 1), ("0", repeats)):
+    for flags, n in ((behind, 1), ("0", repeats)):
         f = "/tmp/stress_%s.npy" % flags
         subprocess.check_call([sys.executable, __file__, "--worker", flags, str(n), f])
         sums[flags] = np.load(f)
-    ref, got = sums["128"], sums["0"].reshape(3, repeats)
+    ref, got = sums[behind], sums["0"].reshape(3, repeats)
     bad = int((got != ref[:, None]).sum())
     print("windows 3, solves per window", repeats, " solves that differ from the sequential arrangement:", bad)
     sys.exit(1 if bad else 0)
