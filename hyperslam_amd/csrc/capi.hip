@@ -135,13 +135,13 @@ int hs_set_spline(hs_problem* p, int order, double t0, double dt, int n_cp, cons
                               p->cp.size() == size_t(8) * n_cp;
   bool same_values = same_structure && std::memcmp(p->cp.data(), cp, sizeof(double) * 8 * n_cp) == 0;
   for (int j = 0; same_values && j < n_cp; ++j) same_values = p->cp_const[j] == (cp_constant ? cp_constant[j] : 0);
-  if (same_values && !p->device_ahead) return HS_OK;  // (nothing to send: the device holds exactly this table)
+  if (same_values && !(p->ahead & hs_problem::vCp)) return HS_OK;  // (nothing to send: the device holds exactly this table)
   p->k = order, p->t0 = t0, p->dt = dt, p->n_cp = n_cp;
   p->cp.assign(cp, cp + size_t(8) * n_cp);
   p->cp_const.assign(n_cp, 0);
   if (cp_constant) p->cp_const.assign(cp_constant, cp_constant + n_cp);
   p->rot_const = rc != 0, p->trans_const = tc != 0;
-  p->touch(same_structure ? unsigned(hs_problem::vCp) : unsigned(hs_problem::kAll));
+  p->touch(same_structure ? unsigned(hs_problem::vCp) : unsigned(hs_problem::kAll), hs_problem::vCp);  // (new knots: everything is re-sent)
   return HS_OK;
 }
 
@@ -234,7 +234,7 @@ int hs_set_landmarks(hs_problem* p, int n, const double* xyz, const uint8_t* con
   p->lm.assign(xyz, xyz + size_t(3) * n);
   p->lm_const.assign(n, 0);
   if (constant) p->lm_const.assign(constant, constant + n);
-  p->touch(same_structure ? unsigned(hs_problem::vLm) : unsigned(hs_problem::vLm | hs_problem::kVis));
+  p->touch(same_structure ? unsigned(hs_problem::vLm) : unsigned(hs_problem::vLm | hs_problem::kVis), hs_problem::vLm);
   return HS_OK;
 }
 
@@ -252,7 +252,7 @@ int hs_set_imu(hs_problem* p, const double* T_bs, const double* i_g, const doubl
   p->bias_g.assign(bias_g, bias_g + size_t(4) * n_bias), p->bias_a.assign(bias_a, bias_a + size_t(4) * n_bias);
   p->bias_const = bias_constant != 0;
   // (new bias knots: the inertial records index them, the border of the reduced system changes size)
-  p->touch(same_structure ? unsigned(hs_problem::vImu | hs_problem::vBias) : unsigned(hs_problem::vImu | hs_problem::vBias | hs_problem::kIne | hs_problem::kTail));
+  p->touch(same_structure ? unsigned(hs_problem::vImu | hs_problem::vBias) : unsigned(hs_problem::vImu | hs_problem::vBias | hs_problem::kIne | hs_problem::kTail), hs_problem::vBias);
   return HS_OK;
 }
 
@@ -321,7 +321,7 @@ int hs_set_gravity(hs_problem* p, const double* g, int constant) {
   const bool same_structure = p->gravity_const == (constant != 0);
   std::memcpy(p->gravity, g, 24);
   p->gravity_const = constant != 0;
-  p->touch(same_structure ? unsigned(hs_problem::vGravity) : unsigned(hs_problem::vGravity | hs_problem::kTail));
+  p->touch(same_structure ? unsigned(hs_problem::vGravity) : unsigned(hs_problem::vGravity | hs_problem::kTail), hs_problem::vGravity);
   return HS_OK;
 }
 
@@ -360,26 +360,14 @@ int hs_set_inertial_residuals(hs_problem* p, int n, const double* st, const doub
 // Same here: rows are appended to / retired from the resident tables when the caller learns of them, hs_stage() sorts and uploads between
 // solves, and an hs_solve() that finds nothing changed sends nothing (the control points, if they were re-sent with new values, only).
 
-/// The host copies of the variables follow the device before a delta call edits the tables next to them (the solve moved the point on the
-/// device; the next structural upload re-sends landmarks in a new order).
-static int pull_state(hs_problem* p) {
-  if (!p->device_ahead || p->dirty) return HS_OK;
-  std::vector<double> a(p->cp.size()), b(p->lm.size()), c(p->bias_g.size()), d(p->bias_a.size());
-  double g[3];
-  int rc = HS_OK;
-  if (!a.empty()) rc = hs_get_control_points(p, a.data());
-  if (!rc && p->n_lm) rc = hs_get_landmarks(p, b.data());
-  if (!rc && p->has_imu) rc = hs_get_bias(p, c.data(), d.data());
-  if (!rc && p->has_imu) rc = hs_get_gravity(p, g);
-  if (!rc) p->device_ahead = false;
-  return rc;
-}
+/// The host copies of the variables follow the device before a delta call edits the tables next to them: a landmark table must not change
+/// size while the device is ahead on it (VarTable), and the next prepare() would fetch what it re-sends in any case.
+static int pull_state(hs_problem* p) { return fetch(p, p->ahead); }
 
 int hs_append_landmarks(hs_problem* p, int n, const double* xyz, const uint8_t* constant, int32_t* first_index) {
   if (!p) return HS_ERR_INVALID;
   if (n < 0 || (n && !xyz)) HS_FAIL(HS_ERR_INVALID, "bad landmark rows");
-  const int rc = pull_state(p);
-  if (rc) return rc;
+  if (const int rc = pull_state(p)) return rc;
   if (first_index) *first_index = p->n_lm;
   if (n == 0) return HS_OK;
   p->lm.insert(p->lm.end(), xyz, xyz + size_t(3) * n);
@@ -393,8 +381,7 @@ int hs_append_pixel_residuals(hs_problem* p, int n, const double* st, const doub
   if (!p) return HS_ERR_INVALID;
   if (n < 0 || (n && (!st || !px || !lm || !cam))) HS_FAIL(HS_ERR_INVALID, "bad pixel residual rows");
   if (n == 0) return HS_OK;
-  const int rc = pull_state(p);
-  if (rc) return rc;
+  if (const int rc = pull_state(p)) return rc;
   p->px_stamp.insert(p->px_stamp.end(), st, st + n), p->px_meas.insert(p->px_meas.end(), px, px + size_t(2) * n);
   p->px_lm.insert(p->px_lm.end(), lm, lm + n), p->px_cam.insert(p->px_cam.end(), cam, cam + n);
   p->touch(hs_problem::kVis | hs_problem::kTail);
@@ -404,8 +391,7 @@ int hs_append_bearing_residuals(hs_problem* p, int n, const double* st, const do
   if (!p) return HS_ERR_INVALID;
   if (n < 0 || (n && (!st || !b || !lm || !cam))) HS_FAIL(HS_ERR_INVALID, "bad bearing residual rows");
   if (n == 0) return HS_OK;
-  const int rc = pull_state(p);
-  if (rc) return rc;
+  if (const int rc = pull_state(p)) return rc;
   p->br_stamp.insert(p->br_stamp.end(), st, st + n), p->br_meas.insert(p->br_meas.end(), b, b + size_t(3) * n);
   p->br_lm.insert(p->br_lm.end(), lm, lm + n), p->br_cam.insert(p->br_cam.end(), cam, cam + n);
   p->touch(hs_problem::kVis | hs_problem::kTail);
@@ -415,8 +401,7 @@ int hs_append_prior_residuals(hs_problem* p, int n, const double* st, const doub
   if (!p) return HS_ERR_INVALID;
   if (n < 0 || (n && (!st || !poses || !sensor))) HS_FAIL(HS_ERR_INVALID, "bad prior residual rows");
   if (n == 0) return HS_OK;
-  const int rc = pull_state(p);
-  if (rc) return rc;
+  if (const int rc = pull_state(p)) return rc;
   p->pr_stamp.insert(p->pr_stamp.end(), st, st + n), p->pr_meas.insert(p->pr_meas.end(), poses, poses + size_t(7) * n);
   p->pr_sensor.insert(p->pr_sensor.end(), sensor, sensor + n);
   p->touch(hs_problem::kPri | hs_problem::kTail);
@@ -426,8 +411,7 @@ int hs_append_inertial_residuals(hs_problem* p, int n, const double* st, const d
   if (!p) return HS_ERR_INVALID;
   if (n < 0 || (n && (!st || !m))) HS_FAIL(HS_ERR_INVALID, "bad inertial residual rows");
   if (n == 0) return HS_OK;
-  const int rc = pull_state(p);
-  if (rc) return rc;
+  if (const int rc = pull_state(p)) return rc;
   p->in_stamp.insert(p->in_stamp.end(), st, st + n), p->in_meas.insert(p->in_meas.end(), m, m + size_t(6) * n);
   p->touch(hs_problem::kIne | hs_problem::kTail);
   return HS_OK;
@@ -445,8 +429,7 @@ int hs_retire_landmarks(hs_problem* p, int n, const int32_t* ids, int32_t* remap
     for (int t = 0; t < n_old; ++t) remap[t] = t;
     return HS_OK;
   }
-  const int rc = pull_state(p);
-  if (rc) return rc;
+  if (const int rc = pull_state(p)) return rc;
   for (int t = 0; t < n_old; ++t) remap[t] = 0;
   for (int i = 0; i < n; ++i) remap[ids[i]] = -1;
   int w = 0;
@@ -469,8 +452,7 @@ int hs_retire_landmarks(hs_problem* p, int n, const int32_t* ids, int32_t* remap
 int hs_retire_residuals_before(hs_problem* p, int type, double stamp) {
   if (!p) return HS_ERR_INVALID;
   if (type < HS_PIXEL || type > HS_INERTIAL) HS_FAIL(HS_ERR_INVALID, "unknown factor type");
-  const int rc = pull_state(p);  // (the variables stay where the last solve left them)
-  if (rc) return rc;
+  if (const int rc = pull_state(p)) return rc;  // (the variables stay where the last solve left them)
   int dropped = 0;
   switch (type) {
     case HS_PIXEL: dropped = drop_rows(int(p->px_stamp.size()), [&](int i) { return p->px_stamp[i] < stamp; }, &p->px_stamp, &p->px_meas, 2, &p->px_lm, &p->px_cam); break;
@@ -1066,22 +1048,18 @@ int hs_solve(hs_problem* p, int max_iterations, hs_summary* summary, hs_iteratio
   }
   DevState& st = *p->h_state;
   const auto host_t4 = std::chrono::steady_clock::now();
+  const VarTables vars = variable_tables(p);
   if (p->want_results) {  // [cp | lm (device order) | bias_g | bias_a | gravity] -> pinned host memory, behind the last kernel
-    const size_t n_cp8 = p->cp.size(), n_lm3 = p->lm.size(), n_b = p->has_imu ? p->bias_g.size() : 0, total = n_cp8 + n_lm3 + 2 * n_b + 3;
+    result_offsets(vars, p->result_off);
+    const size_t total = p->result_off[5];
     if (total > p->h_result_cap) {
       if (p->h_result) (void)hipHostFree(p->h_result);
       p->h_result = nullptr, p->h_result_cap = 0;
       HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p->h_result), 2 * total * sizeof(double), hipHostMallocDefault));
       p->h_result_cap = 2 * total;
     }
-    double* h = p->h_result;
-    HIP_TRY(hipMemcpyAsync(h, p->d_cp.p, n_cp8 * 8, hipMemcpyDeviceToHost, s));
-    if (n_lm3) HIP_TRY(hipMemcpyAsync(h + n_cp8, p->d_lm.p, n_lm3 * 8, hipMemcpyDeviceToHost, s));
-    if (n_b) {
-      HIP_TRY(hipMemcpyAsync(h + n_cp8 + n_lm3, p->d_bias_g.p, n_b * 8, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipMemcpyAsync(h + n_cp8 + n_lm3 + n_b, p->d_bias_a.p, n_b * 8, hipMemcpyDeviceToHost, s));
-    }
-    if (p->has_imu) HIP_TRY(hipMemcpyAsync(h + n_cp8 + n_lm3 + 2 * n_b, p->d_gravity.p, 24, hipMemcpyDeviceToHost, s));  // also with an empty bias table
+    for (int i = 0; i < 5; ++i)
+      if (vars[i].present) HIP_TRY(hipMemcpyAsync(p->h_result + p->result_off[i], vars[i].dev->p, vars[i].len * 8, hipMemcpyDeviceToHost, s));
   }
   // Estimated cameras: the host table follows the device right here (16 doubles per camera), so hs_get_cameras, the result cache, a later
   // upload of the camera table and the evaluation calls that send it (hs_process_tracks, hs_sample_trajectory) all see the estimate.
@@ -1093,7 +1071,7 @@ int hs_solve(hs_problem* p, int max_iterations, hs_summary* summary, hs_iteratio
   HIP_TRY(hipMemcpyAsync(&st, p->d_state.p, sizeof(st), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (imu_back) unpack_imu(p, p->imu_readback);
-  if (max_iterations > 0) p->device_ahead = true;
+  if (max_iterations > 0) p->ahead = present_tables(vars);
   p->results_cached = p->want_results;  // only once every copy above has completed: a failed copy or synchronisation leaves the getters on the device path
   if (p->host_timing) {
     const auto host_t5 = std::chrono::steady_clock::now();
@@ -1151,17 +1129,10 @@ int hs_snapshot(hs_problem* p) {
   if (!p) return HS_ERR_INVALID;
   int rc = prepare(p);
   if (rc) return rc;
-  HIP_TRY(p->d_cp_snap.reserve(p->cp.size()));
-  HIP_TRY(p->d_lm_snap.reserve(p->lm.size() + 1));
-  HIP_TRY(hipMemcpyAsync(p->d_cp_snap.p, p->d_cp.p, p->cp.size() * 8, hipMemcpyDeviceToDevice, p->stream));
-  if (p->n_lm) HIP_TRY(hipMemcpyAsync(p->d_lm_snap.p, p->d_lm.p, p->lm.size() * 8, hipMemcpyDeviceToDevice, p->stream));
-  if (p->has_imu) {
-    HIP_TRY(p->d_bias_g_snap.reserve(p->bias_g.size() + 1));
-    HIP_TRY(p->d_bias_a_snap.reserve(p->bias_a.size() + 1));
-    HIP_TRY(p->d_gravity_snap.reserve(3));
-    HIP_TRY(hipMemcpyAsync(p->d_bias_g_snap.p, p->d_bias_g.p, p->bias_g.size() * 8, hipMemcpyDeviceToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(p->d_bias_a_snap.p, p->d_bias_a.p, p->bias_a.size() * 8, hipMemcpyDeviceToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(p->d_gravity_snap.p, p->d_gravity.p, 24, hipMemcpyDeviceToDevice, p->stream));
+  for (const VarTable& t : variable_tables(p)) {
+    if (!t.present) continue;
+    HIP_TRY(t.snap->reserve(t.len));
+    HIP_TRY(hipMemcpyAsync(t.snap->p, t.dev->p, t.len * 8, hipMemcpyDeviceToDevice, p->stream));
   }
   p->cam_snap = p->cam;  // (the host table equals the device's: hs_solve keeps it so)
   if (p->has_imu) p->imu_snap = pack_imu(p);  // (likewise)
@@ -1172,16 +1143,13 @@ int hs_snapshot(hs_problem* p) {
 
 int hs_restore(hs_problem* p) {
   if (!p) return HS_ERR_INVALID;
-  if (!p->has_snapshot || p->dirty) HS_FAIL(HS_ERR_STATE, "hs_restore without a valid hs_snapshot");
+  if (!p->has_snapshot || p->changed) HS_FAIL(HS_ERR_STATE, "hs_restore without a valid hs_snapshot");
   p->results_cached = false;
   p->cov_valid = false;
-  HIP_TRY(hipMemcpyAsync(p->d_cp.p, p->d_cp_snap.p, p->cp.size() * 8, hipMemcpyDeviceToDevice, p->stream));
-  if (p->n_lm) HIP_TRY(hipMemcpyAsync(p->d_lm.p, p->d_lm_snap.p, p->lm.size() * 8, hipMemcpyDeviceToDevice, p->stream));
-  if (p->has_imu) {
-    HIP_TRY(hipMemcpyAsync(p->d_bias_g.p, p->d_bias_g_snap.p, p->bias_g.size() * 8, hipMemcpyDeviceToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(p->d_bias_a.p, p->d_bias_a_snap.p, p->bias_a.size() * 8, hipMemcpyDeviceToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(p->d_gravity.p, p->d_gravity_snap.p, 24, hipMemcpyDeviceToDevice, p->stream));
-  }
+  const VarTables vars = variable_tables(p);
+  for (const VarTable& t : vars)
+    if (t.present) HIP_TRY(hipMemcpyAsync(t.dev->p, t.snap->p, t.len * 8, hipMemcpyDeviceToDevice, p->stream));
+  p->ahead = present_tables(vars);  // (the device went back to the snapshot, the host tables did not)
   if (p->cam != p->cam_snap && p->cam.size() == p->cam_snap.size()) {  // cameras estimated since the snapshot
     p->cam = p->cam_snap;
     HIP_TRY(hipMemcpyAsync(p->d_cam.p, p->cam.data(), p->cam.size() * 8, hipMemcpyHostToDevice, p->stream));
@@ -1247,7 +1215,7 @@ int hs_exchange_info(hs_problem* p, int32_t* rccl_ranks, int64_t* doubles_per_li
     }
     *rccl_ranks = n;
   }
-  if (doubles_per_linearisation) *doubles_per_linearisation = p->dirty ? 0 : p->T.x_count1;
+  if (doubles_per_linearisation) *doubles_per_linearisation = p->changed ? 0 : p->T.x_count1;
   if (doubles_per_decision) *doubles_per_decision = 5;
   return HS_OK;
 }
@@ -1272,70 +1240,28 @@ int hs_band_blocks(hs_problem* p) {
   return p->T.bw;
 }
 
+/// The getters: the host table, once it has caught up with the device (fetch).
 int hs_get_control_points(hs_problem* p, double* cp) {
   if (!p || !cp) return HS_ERR_INVALID;
-  if (p->dirty) {
-    std::memcpy(cp, p->cp.data(), p->cp.size() * 8);
-    return HS_OK;
-  }
-  if (p->results_cached) {
-    std::memcpy(cp, p->h_result, p->cp.size() * 8);
-  } else {
-    p->want_results = true;
-    HIP_TRY(hipMemcpyAsync(cp, p->d_cp.p, size_t(8) * p->n_cp * 8, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-  }
-  std::memcpy(p->cp.data(), cp, p->cp.size() * 8);
+  if (const int rc = fetch(p, hs_problem::vCp)) return rc;
+  std::memcpy(cp, p->cp.data(), p->cp.size() * 8);
   return HS_OK;
 }
 int hs_get_landmarks(hs_problem* p, double* xyz) {
   if (!p || !xyz) return HS_ERR_INVALID;
-  if (p->dirty || p->n_lm == 0) {
-    std::memcpy(xyz, p->lm.data(), p->lm.size() * 8);
-    return HS_OK;
-  }
-  std::vector<double> fetched;
-  const double* dev = p->h_result + p->cp.size();
-  if (!p->results_cached) {
-    p->want_results = true;
-    fetched.resize(size_t(3) * p->n_lm);
-    HIP_TRY(hipMemcpyAsync(fetched.data(), p->d_lm.p, fetched.size() * 8, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    dev = fetched.data();
-  }
-  for (int d = 0; d < p->n_lm; ++d) {
-    const int t = p->vs.table_of_dev[d];
-    for (int c = 0; c < 3; ++c) xyz[3 * t + c] = p->lm[3 * t + c] = dev[3 * d + c];
-  }
+  if (const int rc = fetch(p, hs_problem::vLm)) return rc;
+  std::memcpy(xyz, p->lm.data(), p->lm.size() * 8);
   return HS_OK;
 }
 int hs_get_bias(hs_problem* p, double* bg, double* ba) {
   if (!p || !bg || !ba) return HS_ERR_INVALID;
-  if (!p->dirty && p->has_imu && !p->bias_g.empty()) {
-    if (p->results_cached) {
-      const double* h = p->h_result + p->cp.size() + p->lm.size();
-      std::memcpy(p->bias_g.data(), h, p->bias_g.size() * 8), std::memcpy(p->bias_a.data(), h + p->bias_g.size(), p->bias_a.size() * 8);
-    } else {
-      p->want_results = true;
-      HIP_TRY(hipMemcpyAsync(p->bias_g.data(), p->d_bias_g.p, p->bias_g.size() * 8, hipMemcpyDeviceToHost, p->stream));
-      HIP_TRY(hipMemcpyAsync(p->bias_a.data(), p->d_bias_a.p, p->bias_a.size() * 8, hipMemcpyDeviceToHost, p->stream));
-      HIP_TRY(hipStreamSynchronize(p->stream));
-    }
-  }
+  if (const int rc = fetch(p, hs_problem::vBias)) return rc;
   std::memcpy(bg, p->bias_g.data(), p->bias_g.size() * 8), std::memcpy(ba, p->bias_a.data(), p->bias_a.size() * 8);
   return HS_OK;
 }
 int hs_get_gravity(hs_problem* p, double* g) {
   if (!p || !g) return HS_ERR_INVALID;
-  if (!p->dirty && p->has_imu) {
-    if (p->results_cached) {
-      std::memcpy(p->gravity, p->h_result + p->cp.size() + p->lm.size() + 2 * p->bias_g.size(), 24);
-    } else {
-      p->want_results = true;
-      HIP_TRY(hipMemcpyAsync(p->gravity, p->d_gravity.p, 24, hipMemcpyDeviceToHost, p->stream));
-      HIP_TRY(hipStreamSynchronize(p->stream));
-    }
-  }
+  if (const int rc = fetch(p, hs_problem::vGravity)) return rc;
   std::memcpy(g, p->gravity, 24);
   return HS_OK;
 }
@@ -1366,7 +1292,7 @@ int hs_cost_function_evaluate(hs_problem* p, int type, int idx, const double* co
   q->px_stamp.clear(), q->px_meas.clear(), q->px_lm.clear(), q->px_cam.clear(), q->br_stamp.clear(), q->br_meas.clear(), q->br_lm.clear(), q->br_cam.clear();
   q->pr_stamp.clear(), q->pr_meas.clear(), q->pr_sensor.clear(), q->in_stamp.clear(), q->in_meas.clear();
   q->has_imu = false, q->n_bias = 0, q->bias_g.clear(), q->bias_a.clear(), q->n_lm = 0, q->lm.clear(), q->lm_const.clear();
-  q->touch(hs_problem::kAll);
+  q->touch(hs_problem::kAll, hs_problem::vLm | hs_problem::vBias);
   int rc = HS_OK;
   std::vector<double> cps(size_t(8) * k);
   for (int j = 0; j < k; ++j) std::memcpy(&cps[8 * j], parameters[j], 64);

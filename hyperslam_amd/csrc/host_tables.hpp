@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
@@ -214,14 +215,15 @@ struct hs_problem {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   std::string err;
-  bool dirty = true;  // tables changed since the last prepare()
-  // What changed (prepare() redoes only that). Structure sections: the sorted visual / prior / inertial tables; kTail = sizes + Tables only.
+  // What changed since the last prepare() (it redoes only that; 0: the device tables are those of the host). Structure sections: the sorted visual / prior / inertial tables; kTail = sizes + Tables only.
   // Values: tables whose content changed while every size, index and sort order stayed (a sliding window re-sends the control points before
   // every solve; the delta interface — hs_append_* / hs_retire_* / hs_stage — keeps the rest resident between solves).
   enum : unsigned { kVis = 1, kPri = 2, kIne = 4, kTail = 8, kStructure = 15, vCp = 16, vCam = 32, vSensor = 64, vLm = 128, vImu = 256, vGravity = 512, vBias = 1024, kValues = 2032, kAll = 2047 };
   unsigned changed = kAll;
-  void touch(unsigned what) { changed |= what, dirty = true, cov_valid = false; }
-  bool device_ahead = false;  // hs_solve moved the point on the device and the host copies have not been refreshed since (pull_state)
+  // Variable tables (variable_tables() below) of which the device holds values the host table does not: set by hs_solve and hs_restore, cleared per
+  // table when fetch() brings it to the host or the caller's values replace it (`overwritten`) — never because something else was uploaded.
+  unsigned ahead = 0;
+  void touch(unsigned what, unsigned overwritten = 0) { changed |= what, ahead &= ~overwritten, cov_valid = false; }
 
   // host tables (caller's table order)
   int k = 0, n_cp = 0;
@@ -265,9 +267,11 @@ struct hs_problem {
   double host_prepare[2] = {0, 0};               // (prepare() of the running call)
   // Result read-back: a caller that fetches the state after every solve (the sliding-window driver: control points, landmarks, bias
   // points, gravity = four synchronous copies of ~30 us each) gets it copied into pinned host memory at the end of hs_solve, in the stream,
-  // before the solve's own synchronisation; the getters then read host memory. Enabled by the first getter call that had to go to the device.
+  // before the solve's own synchronisation; fetch() then reads host memory. Enabled by the first fetch() that had to go to the device; consulted
+  // by fetch() alone, i.e. for tables the device is ahead on, whose slice cannot have changed since the copy.
   double* h_result = nullptr;
   size_t h_result_cap = 0;
+  size_t result_off[6] = {0, 0, 0, 0, 0, 0};  // slice of each variable table in h_result as of that copy ([5]: the end)
   bool want_results = false, results_cached = false;
   size_t vb_len = 0;                             // doubles of d_Vb / d_Vb2 in front of their zero pad (prepare())
   int zeroed_np = -1, zeroed_ncb = -1;           // layout / allocations for which the never-written parts of Sb2, Vb, yt were zeroed
@@ -440,6 +444,74 @@ static int imu_columns(const hs_problem* p, std::vector<int>* map) {
   return n;
 }
 
+/// One variable table of the window and where its copies live. variable_tables() lists the five in the order of the read-back buffer,
+/// h_result = [cp | lm (device order) | bias_g | bias_a | gravity]; everything that handles them one by one loops over that list.
+/// Invariant behind hs_problem::ahead: while a table's bit is set, its host table has the size it had at the last structural prepare() and
+/// vs.table_of_dev is the mapping of the resident device table. Every call that resizes a variable table either fetches first
+/// (hs_append_landmarks, hs_retire_landmarks) or overwrites it and thereby clears the bit; fetch() checks it rather than index past a table.
+struct VarTable {
+  unsigned bit;  // in hs_problem::changed and ::ahead (the two bias tables share vBias)
+  double* host;
+  size_t len;  // doubles
+  DBuf<double>*dev, *snap;
+  bool present;       // part of the problem: an absent table is neither copied nor ahead
+  bool device_order;  // device row d is host row vs.table_of_dev[d]
+};
+using VarTables = std::array<VarTable, 5>;
+static VarTables variable_tables(hs_problem* p) {
+  const bool imu = p->has_imu, bias = imu && !p->bias_g.empty();
+  return {{{hs_problem::vCp, p->cp.data(), p->cp.size(), &p->d_cp, &p->d_cp_snap, !p->cp.empty(), false},
+           {hs_problem::vLm, p->lm.data(), p->lm.size(), &p->d_lm, &p->d_lm_snap, p->n_lm > 0, true},
+           {hs_problem::vBias, p->bias_g.data(), p->bias_g.size(), &p->d_bias_g, &p->d_bias_g_snap, bias, false},
+           {hs_problem::vBias, p->bias_a.data(), p->bias_a.size(), &p->d_bias_a, &p->d_bias_a_snap, bias, false},
+           {hs_problem::vGravity, p->gravity, 3, &p->d_gravity, &p->d_gravity_snap, imu, false}}};
+}
+/// The slice of every variable table in h_result: back to back in list order (off[5]: the end).
+static void result_offsets(const VarTables& v, size_t off[6]) {
+  off[0] = 0;
+  for (int i = 0; i < 5; ++i) off[i + 1] = off[i] + v[i].len;
+}
+static unsigned present_tables(const VarTables& v) {
+  unsigned bits = 0;
+  for (const VarTable& t : v) bits |= t.present ? t.bit : 0u;
+  return bits;
+}
+
+/// The host tables in `mask` that the device is ahead on follow it (landmarks back in table order): out of h_result where the last hs_solve
+/// left its copy, otherwise with one copy per table and one synchronisation of the stream.
+static int fetch(hs_problem* p, unsigned mask) {
+  mask &= p->ahead;
+  if (!mask) return HS_OK;
+  const VarTables v = variable_tables(p);
+  const bool cached = p->results_cached;
+  const std::vector<int>& table_of_dev = p->vs.table_of_dev;
+  std::vector<double> rows;  // landmarks as the device holds them
+  for (int i = 0; i < 5; ++i) {
+    const VarTable& t = v[i];
+    if (!(t.bit & mask) || !t.present) continue;
+    if (t.len > t.dev->cap || (cached && t.len != p->result_off[i + 1] - p->result_off[i]) || (t.device_order && t.len != 3 * table_of_dev.size()))
+      HS_FAIL(HS_ERR_STATE, "internal: a variable table changed size while the device held its newest values");
+    if (cached) continue;
+    if (t.device_order) rows.resize(t.len);
+    HIP_TRY(hipMemcpyAsync(t.device_order ? rows.data() : t.host, t.dev->p, t.len * 8, hipMemcpyDeviceToHost, p->stream));
+  }
+  p->want_results |= !cached;
+  if (!cached) HIP_TRY(hipStreamSynchronize(p->stream));
+  for (int i = 0; i < 5; ++i) {
+    const VarTable& t = v[i];
+    if (!(t.bit & mask) || !t.present) continue;
+    const double* src = cached ? p->h_result + p->result_off[i] : rows.data();
+    if (t.device_order) {
+      for (size_t d = 0; d < table_of_dev.size(); ++d)
+        for (int c = 0; c < 3; ++c) t.host[3 * table_of_dev[d] + c] = src[3 * d + c];
+    } else if (cached) {
+      std::memcpy(t.host, src, t.len * 8);
+    }
+  }
+  p->ahead &= ~mask;
+  return HS_OK;
+}
+
 /// Value tables whose content changed (hs_problem::changed): control points + constancy mask, cameras, sensors, landmarks (device order), IMU
 /// parameters, gravity, bias points. Sizes, indices and sort orders are those of the last structural prepare().
 static int upload_values(hs_problem* p, unsigned what) {
@@ -493,7 +565,13 @@ static int upload_values(hs_problem* p, unsigned what) {
 }
 
 int prepare(hs_problem* p) {
-  if (!p->dirty) return HS_OK;
+  // A failed prepare() leaves `changed` as it was: the next one redoes the same sections (the tables of a refused window stay refused).
+  const unsigned what = p->changed;
+  if (!what) return HS_OK;
+  // The value tables this call sends (a structural change of the visual tables re-orders the landmarks on the device: their values go with
+  // it). Where the device is ahead on one of them the host follows first, so that what is sent does not depend on the order of the calls.
+  const unsigned values = (what & hs_problem::kValues) | ((what & hs_problem::kVis) ? unsigned(hs_problem::vLm) : 0u);
+  if (const int rc = fetch(p, values)) return rc;
   struct BatchScope {  // every DBuf::upload below goes through the staging arena; sent in one piece at the end
     UploadBatch* b;
     explicit BatchScope(UploadBatch* x) : b(x) { tl_upload_batch = b; }
@@ -507,13 +585,11 @@ int prepare(hs_problem* p) {
   if (p->k < 4 || p->k > 6) HS_FAIL(HS_ERR_INVALID, "device kernels are instantiated for spline orders 4, 5 and 6");
   HIP_TRY(hipSetDevice(p->device));
   hipStream_t s = p->stream;
-  // A failed prepare() leaves `changed` as it was: the next one redoes the same sections (the tables of a refused window stay refused).
-  const unsigned what = p->changed;
   if (!(what & hs_problem::kStructure)) {  // values only: every size, index and sort order of the resident tables stands
-    const int rc = upload_values(p, what);
+    const int rc = upload_values(p, values);
     if (rc) return rc;
     HIP_TRY(p->batch.flush(s));
-    p->dirty = false, p->changed = 0;
+    p->changed = 0;
     if (p->host_timing) {
       const double t = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
       p->host_prepare[1] += t, p->host_ms[1] += t;
@@ -602,10 +678,7 @@ int prepare(hs_problem* p) {
 
   // ---- upload ----
   const auto host_t1 = std::chrono::steady_clock::now();
-  {  // (a structural change of the visual tables re-orders the landmarks on the device: their values go with it)
-    const int rc = upload_values(p, (what & hs_problem::kValues) | ((what & hs_problem::kVis) ? unsigned(hs_problem::vLm) : 0u));
-    if (rc) return rc;
-  }
+  if (const int rc = upload_values(p, values)) return rc;
   const size_t nl = size_t(std::max(p->n_lm, 1));
   if (what & hs_problem::kVis) {
     HIP_TRY(p->d_lm_ptr.upload(vs.lm_ptr, s));
@@ -970,8 +1043,7 @@ int prepare(hs_problem* p) {
   T.rank = p->rank, T.world = p->world;
   T.st = p->d_state.p;
   HIP_TRY(p->batch.flush(s));  // (the staging arena outlives this call: no host synchronisation)
-  p->dirty = false, p->changed = 0;
-  if ((what & hs_problem::kValues) == hs_problem::kValues) p->device_ahead = false;  // (every variable was just sent: host and device agree)
+  p->changed = 0;
   if (p->host_timing) {
     const auto host_t2 = std::chrono::steady_clock::now();
     p->host_prepare[0] = std::chrono::duration<double, std::milli>(host_t1 - host_t0).count();

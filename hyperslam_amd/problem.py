@@ -219,6 +219,28 @@ class Problem:
         self._check(self.lib.set_spline(self.h, w.order, w.t0, w.dt, cp.shape[0], _d(cp), None if cpc is None else _u8(cpc),
                                         int(w.rotation_constant), int(w.translation_constant)), "set_spline")
 
+    def set_landmarks(self, xyz, constant=None):
+        """The landmark table re-sent whole (values + constancy mask)."""
+        lm = _arr(xyz, _f64, (-1, 3))
+        c = None if constant is None else _arr(constant, np.uint8)
+        self._check(self.lib.set_landmarks(self.h, lm.shape[0], _d(lm), None if c is None else _u8(c)), "set_landmarks")
+
+    def set_residuals(self, ftype, stamps, values, landmark=None, camera=None, sensor=None):
+        """The residual table of one factor type re-sent whole (same columns as append_residuals)."""
+        st = _arr(stamps, _f64)
+        n = st.shape[0]
+        if ftype in (HS_PIXEL, HS_BEARING):
+            v = _arr(values, _f64, (-1, 2 if ftype == HS_PIXEL else 3))
+            li, ci = _arr(landmark, np.int32), _arr(camera, np.int32)
+            fn = self.lib.set_pixel_residuals if ftype == HS_PIXEL else self.lib.set_bearing_residuals
+            self._check(fn(self.h, n, _d(st), _d(v), _i(li), _i(ci)), "set_residuals")
+        elif ftype == HS_PRIOR:
+            v, si = _arr(values, _f64, (-1, 7)), _arr(sensor if sensor is not None else np.zeros(n), np.int32)
+            self._check(self.lib.set_prior_residuals(self.h, n, _d(st), _d(v), _i(si)), "set_residuals")
+        else:
+            v = _arr(values, _f64, (-1, 6))
+            self._check(self.lib.set_inertial_residuals(self.h, n, _d(st), _d(v)), "set_residuals")
+
     # -- structure ---------------------------------------------------------------------------------------------
     def num_residuals(self, ftype):
         return self.lib.num_residuals(self.h, ftype)

@@ -221,8 +221,11 @@ int hs_set_inertial_residuals(hs_problem* p, int n, const double* stamps, const 
  * uploads what changed — between solves, off optimize()'s clock — and an hs_solve() that finds the tables staged uploads nothing
  * (a control-point table re-sent with new values and the same knots costs one small copy).
  * The hs_set_* functions above remain the whole-table form of the same thing; both may be mixed.
- * A delta call first brings the library's host copies of the variables (control points, landmarks, bias points, gravity) up to the
- * result of the last hs_solve, so the state persists across solves without the caller re-sending it. */
+ * The variables (control points, landmarks, bias points, gravity) persist in the library table by table, in whatever order the calls
+ * come: a table stays at the result of the last hs_solve (after hs_restore: at the snapshot) until the caller sends that table again
+ * (hs_set_spline, hs_set_landmarks, hs_set_imu for the bias points, hs_set_gravity), and re-sending one table leaves the others where
+ * they are. The getters, hs_stage and every later call that evaluates the window's residuals (hs_solve, hs_cost, hs_linearize,
+ * hs_reduced_system, hs_compute_covariance) see exactly that state. */
 /* Rows appended to the landmark table; *first_index (nullable) receives the index of the first new row (= the landmark id the residual
  * rows refer to). Replaces addLandmark (optimizer.cpp:347-358). */
 int hs_append_landmarks(hs_problem* p, int n, const double* xyz, const uint8_t* constant, int32_t* first_index);

@@ -208,3 +208,140 @@ def test_hip_state_persists_across_delta_calls(hip, oracle):
         assert A.landmarks().shape == (w.landmarks.shape[0] + 1, 3) and np.array_equal(A.landmarks()[-1], [0.5, 0.25, 2.0])
         assert np.abs(A.landmarks() - O.landmarks()).max() < 1e-6
         assert np.abs(A.control_points() - O.control_points()).max() < 1e-6
+
+
+# ---- where the newest copy of each variable table lives: the result must not depend on the order of the calls ---------------------------
+# (include/hyperslam_hip.h: the variables persist table by table; the oracle keeps them in place. Tolerances: the ones of this file against
+# the oracle, 1e-6 relative on costs and 1e-6 absolute on the state. A "twin" is a second HIP handle given the same calls up to the solve,
+# whose getters are read right after it.)
+
+
+def _half_inertial(w):
+    half = len(w.inertial_stamps) // 2
+    s = copy.copy(w)
+    s.inertial_stamps, s.inertial_measurements = w.inertial_stamps[:half], w.inertial_measurements[:half]
+    return s, half
+
+
+def _read_all(P):
+    return P.control_points(), P.landmarks(), P.bias(), P.gravity()
+
+
+def _switch_result_cache_on(P):
+    """hs_solve copies its result into pinned host memory once a getter had to go to the device for a solved table: the next solve's
+    result is then served from that copy."""
+    P.solve(1)
+    _read_all(P)
+
+
+@pytest.mark.gpu
+def test_hip_state_survives_control_points_resent_before_an_append(hip, oracle):
+    """solve -> control points re-sent (same knots) -> append rows -> stage -> solve: landmarks, bias points and gravity stay where the
+    first solve left them (oracle: 440.1; a handle that re-sends its pre-solve host copies: 752.4)."""
+    w = _window()
+    s, half = _half_inertial(w)
+    with ha.Problem(s) as A, ha.Problem(s, lib=oracle) as O:
+        for P in (A, O):
+            P.solve(3)
+            P.set_control_points(w.control_points, w.cp_constant)
+            P.append_residuals(HS_INERTIAL, w.inertial_stamps[half:], w.inertial_measurements[half:])
+            P.stage()
+        sa, so = A.solve(0), O.solve(0)
+        print("cost after the append: hip %.9g oracle %.9g" % (sa["final_cost"], so["final_cost"]))
+        assert abs(sa["final_cost"] - so["final_cost"]) <= 1e-6 * so["final_cost"]
+        sa, so = A.solve(3), O.solve(3)
+        assert abs(sa["initial_cost"] - so["initial_cost"]) <= 1e-6 * so["initial_cost"]
+        assert abs(sa["final_cost"] - so["final_cost"]) <= 1e-6 * so["final_cost"]
+        assert np.abs(A.control_points() - O.control_points()).max() < 1e-6
+        assert np.abs(A.landmarks() - O.landmarks()).max() < 1e-6
+        assert np.abs(A.bias()[0] - O.bias()[0]).max() < 1e-6 and np.abs(A.bias()[1] - O.bias()[1]).max() < 1e-6
+        assert np.abs(A.gravity() - O.gravity()).max() < 1e-6
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("resent", ["grown_spline", "pixel_rows"])
+def test_hip_state_survives_a_structural_resend(hip, oracle, resent):
+    """solve -> the solved control points re-sent with one more row at the end (new knots: everything is re-sent), or the unchanged pixel
+    rows re-sent whole (the landmarks are re-ordered) -> solve(0): the cost is the first solve's final cost (oracle: 39.344; with the
+    solved landmarks, bias points and gravity lost: 527.5)."""
+    w = _window()
+    with ha.Problem(w) as A, ha.Problem(w, lib=oracle) as O:
+        cost = {}
+        for name, P in (("hip", A), ("oracle", O)):
+            first = P.solve(3)
+            if resent == "grown_spline":
+                cp = P.control_points()
+                row = cp[-1].copy()
+                row[4:7] = 2.0 * cp[-1, 4:7] - cp[-2, 4:7]  # position extrapolated, rotation copied
+                row[7] = w.t0 + w.n_cp * w.dt
+                frozen = None if w.cp_constant is None else np.append(np.asarray(w.cp_constant, np.uint8), np.uint8(0))
+                P.set_control_points(np.vstack([cp, row]), frozen)
+            else:
+                P.set_residuals(HS_PIXEL, w.pixel_stamps, w.pixels, landmark=w.pixel_landmark, camera=w.pixel_camera)
+            cost[name] = (first["final_cost"], P.solve(0)["final_cost"])
+        print("first solve / after the re-send: hip %.9g %.9g oracle %.9g %.9g" % (cost["hip"] + cost["oracle"]))
+        assert abs(cost["hip"][1] - cost["oracle"][1]) <= 1e-6 * cost["oracle"][1]
+        assert abs(cost["hip"][1] - cost["oracle"][0]) <= 1e-6 * cost["oracle"][0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cached", [False, True])
+def test_hip_getters_after_control_points_resent(hip, cached):
+    """solve -> set_control_points -> landmarks(), bias(), gravity(): the solved values, bit for bit, out of the pinned result cache (the
+    getters had gone to the device once before the solve) or from the device (never called before)."""
+    w = _window()
+    with ha.Problem(w) as A, ha.Problem(w) as twin:
+        for P in (A, twin):
+            if cached:
+                _switch_result_cache_on(P)
+            P.solve(3)
+        _, lm, (bg, ba), g = _read_all(twin)
+        assert np.abs(lm - w.landmarks).max() > 1e-6  # the solve moved them
+        A.set_control_points(w.control_points, w.cp_constant)
+        assert np.array_equal(A.landmarks(), lm)
+        assert np.array_equal(A.bias()[0], bg) and np.array_equal(A.bias()[1], ba)
+        assert np.array_equal(A.gravity(), g)
+        assert np.array_equal(A.control_points(), w.control_points)
+
+
+@pytest.mark.gpu
+def test_hip_landmarks_resent_are_not_served_from_the_result_cache(hip):
+    """solve -> set_landmarks (new values) -> stage -> landmarks(): the caller's values, not the previous solve's out of the result cache —
+    and they are still there after a delta call; the control points are the solved ones."""
+    w = _window()
+    with ha.Problem(w) as A, ha.Problem(w) as twin:
+        for P in (A, twin):
+            _switch_result_cache_on(P)
+            P.solve(3)
+        mine = w.landmarks + 0.01
+        A.set_landmarks(mine, w.landmark_constant)
+        A.stage()
+        assert np.array_equal(A.landmarks(), mine)
+        assert np.array_equal(A.control_points(), twin.control_points())
+        extra = np.array([[0.5, 0.25, 2.0]])  # unobserved
+        assert A.append_landmarks(extra) == len(mine)
+        A.stage()
+        assert np.array_equal(A.landmarks(), np.vstack([mine, extra]))
+        assert np.array_equal(A.control_points(), twin.control_points())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("read_solved", [False, True])
+def test_hip_restored_state_survives_resend_and_append(hip, oracle, read_solved):
+    """snapshot -> solve -> restore -> control points re-sent (snapshot values) -> append rows -> stage -> solve(0): the restored device
+    state is what survives, not the solved host copies (read_solved: the getters brought them to the host before the restore) — the cost
+    of the initial window with those rows."""
+    w = _window()
+    s, half = _half_inertial(w)
+    with ha.Problem(s) as A, ha.Problem(w, lib=oracle) as O:
+        A.snapshot()
+        A.solve(2)
+        if read_solved:
+            assert np.abs(_read_all(A)[1] - w.landmarks).max() > 1e-6
+        A.restore()
+        A.set_control_points(w.control_points, w.cp_constant)
+        A.append_residuals(HS_INERTIAL, w.inertial_stamps[half:], w.inertial_measurements[half:])
+        A.stage()
+        sa, so = A.solve(0), O.solve(0)
+        print("cost after the restore: hip %.9g oracle %.9g" % (sa["final_cost"], so["final_cost"]))
+        assert abs(sa["final_cost"] - so["final_cost"]) <= 1e-6 * so["final_cost"]
