@@ -19,6 +19,7 @@ HS_INERTIAL_AS_REFERENCE, HS_INERTIAL_EXACT = 0, 1  # hs_set_inertial_jacobian
 (HS_MANIFOLD_CONSTANT, HS_MANIFOLD_EUCLIDEAN, HS_MANIFOLD_CONTROL_POINT, HS_MANIFOLD_SE3, HS_MANIFOLD_SPHERE3,
  HS_MANIFOLD_BIAS_POINT) = range(6)
 HS_NO_CONVERGENCE, HS_CONVERGENCE, HS_FAILURE = 0, 1, 2
+HS_SENSOR_CAMERA, HS_SENSOR_IMU, HS_SENSOR_PLAIN = 0, 1, 2  # hs_sample_sensor_covariance
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
@@ -155,6 +156,8 @@ _PRODUCT_ONLY = {
     "get_covariance": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "get_covariance_cross": (C.c_int, [C.c_void_p, c_double_p]),
     "sample_covariance": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
+    "set_imu_covariance": (C.c_int, [C.c_void_p, C.c_int]),
+    "sample_sensor_covariance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p]),
     # stereo KLT front-end (hs_tracker handle; the oracle has no counterpart)
     "tracker_default_options": (C.c_int, [C.c_void_p]),
     "tracker_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -286,6 +286,16 @@ int hs_set_imu_estimation(hs_problem* p, int enabled) {
   return HS_OK;
 }
 
+/// hs_compute_covariance takes the free IMU blocks of this handle (off by default: it refuses them).
+int hs_set_imu_covariance(hs_problem* p, int enabled) {
+  if (!p) return HS_ERR_INVALID;
+  const bool on = enabled != 0;
+  if (on == p->imu_covariance) return HS_OK;
+  p->imu_covariance = on;
+  if (imu_columns(p, nullptr)) p->cov_valid = false;  // (no table depends on it: the build is hs_reduced_system's either way)
+  return HS_OK;
+}
+
 /// The host copies: hs_solve keeps them equal to the device's parameters.
 int hs_get_imu(hs_problem* p, double* T_bs, double* i_g, double* i_a, double* S_g, double* X_a) {
   if (!p) return HS_ERR_INVALID;
@@ -815,11 +825,18 @@ int hs_compute_covariance(hs_problem* p) {
   if (!p) return HS_ERR_INVALID;
   if (p->has_weights()) HS_FAIL(HS_ERR_INVALID, kWeightsMessage);
   if (p->world > 1) HS_FAIL(HS_ERR_STATE, "hs_compute_covariance: sharded handles (world > 1) are not supported");
-  if (imu_columns(p, nullptr))  // (whatever hs_set_camera_covariance says)
+  const bool free_imu = imu_columns(p, nullptr) > 0;
+  if (!p->imu_covariance && free_imu)  // (taking them is opt-in per handle: hs_set_imu_covariance; whatever hs_set_camera_covariance says)
     HS_FAIL(HS_ERR_STATE, "hs_compute_covariance: free IMU blocks (hs_set_imu_constancy) are not supported; hs_reduced_system builds their system "
                           "(DESIGN.md section 14)");
   if (!p->cam_covariance && camera_columns(p, nullptr))  // (taking them is opt-in per handle: hs_set_camera_covariance)
     HS_FAIL(HS_ERR_STATE, "hs_compute_covariance: free camera blocks (hs_set_camera_constancy) are not supported");
+  // a_m = a_i + diag(F_a (X_a (+) t_bs)) (inertial.cpp:128): the translation of T_bs and X_a enter the accelerometer model through their sum
+  // only, so without damping their twelve columns are exactly dependent — and the pivot test of k_cov_band, relative to a scaled X_a diagonal
+  // of ~1e-6, is not guaranteed to see it. Decided here, before any launch. (hs_solve damps: it estimates both.)
+  if (free_imu && !p->imu_const[0] && !p->imu_const[4])
+    HS_FAIL(HS_ERR_NUMERIC, "hs_compute_covariance: rank deficient with the IMU blocks T_bs and X_a both free: the accelerometer model depends on the "
+                            "translation of T_bs and on the columns of X_a through their sum only (hold one of the two constant, hs_set_imu_constancy)");
   p->cov_valid = false;
   int rc = prepare(p);
   if (rc) return rc;
@@ -832,7 +849,7 @@ int hs_compute_covariance(hs_problem* p) {
   const Tables& T = p->T;
   const int np = T.np, ncb = 6 * T.bw, nb = T.nb, n_lm = T.n_lm;
   if (T.bw < p->k) HS_FAIL(HS_ERR_NUMERIC, "hs_compute_covariance: no residual couples the control points of one spline segment");
-  const int nbi = nb - T.nc;  // bias splines + gravity; the camera columns behind them are free coordinates (camera_columns)
+  const int nbi = nb - p->ni - T.nc;  // bias splines + gravity; the IMU and the camera columns behind them are free coordinates (imu_columns, camera_columns)
   std::vector<uint8_t> cc(size_t(np) + nb, 0);  // constant coordinates: control points (whole or rotation / translation), bias splines, gravity
   for (int r = 0; r < np; ++r) cc[r] = p->cp_const[r / 6] || (r % 6 < 3 ? p->rot_const : p->trans_const);
   for (int b = 0; b < nbi; ++b) cc[np + b] = b < 6 * p->n_bias ? p->bias_const != 0 : p->gravity_const != 0;
@@ -880,9 +897,19 @@ int hs_compute_covariance(hs_problem* p) {
     if (c < np)
       HS_FAIL(HS_ERR_NUMERIC, "hs_compute_covariance: rank deficient at control point " + std::to_string(c / 6) + " (local coordinate " +
                                   std::to_string(c % 6) + "): a free coordinate without information (gauge not fixed, or no residual touches it)");
+    if (c - np >= nbi && c - np < nbi + p->ni) {
+      static const char* const block[5] = {"T_bs", "i_g", "i_a", "S_g", "X_a"};
+      static const int first[5] = {0, 36, 72, 108, 162};  // (imu_columns: entry of row 0 of the column inside a record of sensor Jacobians)
+      const int e = p->imucal_map[c - np - nbi] & 0xffff;
+      int b = 4;
+      while (b > 0 && e < first[b]) --b;
+      HS_FAIL(HS_ERR_NUMERIC, "hs_compute_covariance: rank deficient at border unknown " + std::to_string(c - np) + " (IMU " + block[b] + " coordinate " +
+                                  std::to_string(e - first[b]) +
+                                  "): a free IMU coordinate without information (no inertial row of the window depends on it, or the window does not fix it)");
+    }
     if (c - np >= nbi) {
       static const char* const block[3] = {"T_bs", "intrinsics", "distortion"};
-      const int m = p->calib_map[c - np - nbi], col = m & 0xff, b = col < 6 ? 0 : (col < 10 ? 1 : 2);
+      const int m = p->calib_map[c - np - nbi - p->ni], col = m & 0xff, b = col < 6 ? 0 : (col < 10 ? 1 : 2);
       HS_FAIL(HS_ERR_NUMERIC, "hs_compute_covariance: rank deficient at border unknown " + std::to_string(c - np) + " (camera " + std::to_string(m >> 8) +
                                   ", " + block[b] + " coordinate " + std::to_string(col - (b == 0 ? 0 : (b == 1 ? 6 : 10))) +
                                   "): a free camera coordinate without information (no residual of the window depends on it, or the window does not fix it)");
@@ -953,6 +980,50 @@ int hs_sample_covariance(hs_problem* p, int n, const double* stamps, double* cov
   HIP_TRY(d_out.reserve(size_t(36) * n));
   const int grid = (n + kBlock / 64 - 1) / (kBlock / 64);
   HS_ORDER_SWITCH(k, k_cov_sample<K><<<grid, kBlock, 0, s>>>(p->T, p->d_cov_band.p, n, d_st.p, d_out.p));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(cov, d_out.p, size_t(36) * n * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return HS_OK;
+}
+
+/// Covariance of the sensor pose T_wb(t) o T_bs (k_cov_sample_sensor). The sensor's T_bs is read where the device keeps it — the estimate after
+/// an hs_solve —; its columns of the computed covariance enter when it is one of its free unknowns, and column offset -1 says it is not.
+int hs_sample_sensor_covariance(hs_problem* p, int kind, int index, int n, const double* stamps, double* cov) {
+  if (!p || n < 0 || (n && (!stamps || !cov))) return HS_ERR_INVALID;
+  if (kind != HS_SENSOR_CAMERA && kind != HS_SENSOR_IMU && kind != HS_SENSOR_PLAIN) HS_FAIL(HS_ERR_INVALID, "hs_sample_sensor_covariance: unknown sensor kind");
+  const int count = kind == HS_SENSOR_CAMERA ? p->n_cam : (kind == HS_SENSOR_IMU ? (p->has_imu ? 1 : 0) : p->n_sensor);
+  if (index < 0 || index >= count)
+    HS_FAIL(HS_ERR_INVALID, "hs_sample_sensor_covariance: sensor index " + std::to_string(index) + " outside its table (" + std::to_string(count) + " entries)");
+  if (!p->cov_valid) HS_FAIL(HS_ERR_STATE, "hs_sample_sensor_covariance: no covariance of the current state (call hs_compute_covariance after the last change)");
+  if (n == 0) return HS_OK;
+  const int k = p->k, n_seg = p->n_cp - k + 1;
+  for (int i = 0; i < n; ++i) {
+    const int f = h_segment_first(stamps[i], p->t0, p->dt, k);
+    if (f < 0 || f >= n_seg) HS_FAIL(HS_ERR_INVALID, "stamp outside the valid range of the spline");
+  }
+  // (cov_valid: the tables are those of the last prepare() — ni, nc and their maps describe the border of the computed covariance)
+  const Tables& T = p->T;
+  const int nb = p->cov_nb, nbi = nb - p->ni - p->nc;
+  const double* T_bs = nullptr;
+  int ecol = -1;
+  if (kind == HS_SENSOR_CAMERA) {
+    T_bs = T.cam + size_t(kCamStride) * index;
+    for (int c = 0; c < p->nc && ecol < 0; ++c)
+      if (p->calib_map[c] == (index << 8)) ecol = nbi + p->ni + c;  // (local column 0: the camera's T_bs block is free, six columns from here)
+  } else if (kind == HS_SENSOR_IMU) {
+    T_bs = reinterpret_cast<const double*>(T.imu) + offsetof(ImuParams, T_bs) / sizeof(double);
+    if (p->ni && !p->imu_const[0]) ecol = nbi;  // (T_bs is the first block of the IMU columns)
+  } else {
+    T_bs = T.sensor + size_t(8) * index;
+  }
+  if (ecol >= 0 && ecol + 6 > nb) HS_FAIL(HS_ERR_STATE, "hs_sample_sensor_covariance: the border of the computed covariance does not hold the sensor's T_bs");
+  hipStream_t s = p->stream;
+  DBuf<double> d_st, d_out;
+  std::vector<double> st(stamps, stamps + n);
+  HIP_TRY(d_st.upload(st, s));
+  HIP_TRY(d_out.reserve(size_t(36) * n));
+  const int grid = (n + kBlock / 64 - 1) / (kBlock / 64);
+  HS_ORDER_SWITCH(k, k_cov_sample_sensor<K><<<grid, kBlock, 0, s>>>(T, p->d_cov_band.p, p->d_cov_pb.p, p->d_cov_bb.p, nb, T_bs, ecol, n, d_st.p, d_out.p));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(cov, d_out.p, size_t(36) * n * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));

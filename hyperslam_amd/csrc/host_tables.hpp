@@ -345,6 +345,7 @@ struct hs_problem {
   DBuf<int> d_imucal_map;
   DBuf<double> d_imucal_rec, d_imucal_part;
   bool imu_estimation = false;   // hs_set_imu_estimation: hs_solve estimates the free blocks (off: it refuses a handle that has one)
+  bool imu_covariance = false;   // hs_set_imu_covariance: hs_compute_covariance takes the free blocks (off: it refuses a handle that has one)
   bool imu_estimated() const { return ni > 0 && imu_estimation; }  // (ni: as of the last prepare())
   DBuf<ImuParams> d_imu_cand;    // candidate IMU parameters next to d_imu (k_imucal_candidate), on handles that estimate IMU blocks only
   ImuParams imu_readback;        // hs_solve: the device parameters on their way into the host copies (imu_T_bs ..)

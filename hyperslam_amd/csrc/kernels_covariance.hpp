@@ -15,6 +15,8 @@
 //   k_cov_landmarks_cam (wave/landmark)  the same with free camera coordinates in the border (hs_set_camera_covariance): G = [Yh ; Y_c'] over
 //                                     the landmark's pose rows and the camera columns, Sigma from the band, Sigma_pb and Sigma_bb
 //   k_cov_sample     (wave/stamp)     J(t) Sigma_cp J(t)', J(t) = the state Jacobian of the pose prior with its measurement at the pose at t
+//   k_cov_sample_sensor (wave/stamp)  the same for a sensor pose T_wb(t) o T_bs; a free T_bs (camera, IMU) adds its columns of Sigma_pb and its
+//                                     block of Sigma_bb through the extrinsics Jacobian (hs_sample_sensor_covariance)
 // Constant coordinates are decoupled rows (identity in the factor, zero covariance); a free coordinate whose pivot is not positive or falls
 // below kCovPivotTol of its scaled diagonal — the build's marker 1.0 of a structurally zero column included — ends the factorisation and
 // is reported through CovBand::status. Owner-computes everywhere, one fixed order per sum: two computations are bit-identical.
@@ -474,6 +476,122 @@ __global__ void __launch_bounds__(kBlock) k_cov_sample(Tables T, const double* c
     const int a = lane / 6, b = lane % 6;
     double v = 0.0;
     for (int c = 0; c < 6 * K; ++c) v = fma(JS[w][a * 6 * K + c], J[b * 6 * K + c], v);
+    out[36 * size_t(i) + lane] = v;
+  }
+}
+
+/// v, as a value the optimiser cannot trace back to the expression it came from (through the scalar registers; for a single active lane).
+HSD double cov_opaque(double v) {
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
+/// One wave per stamp: the covariance of the SENSOR pose T_ws(t) = T_wb(t) o T_bs (manifold.cpp:54), in the residual coordinates of the pose
+/// prior with its measurement at that pose. With J_s (6 x 6K) the state Jacobian of prior_linearize for the sensor and J_e (6 x 6) its
+/// Jacobian in the Ceres-local coordinates of T_bs (prior_sensor_jacobians: [2 J_r^-1 R_sb, 0 ; 0, R_wb]), J = [J_s | J_e] and
+///   out = J Sigma_aug J',   Sigma_aug = [Sigma_pp, Sigma_pe ; Sigma_pe', Sigma_ee]
+/// over the K control points of the segment and the six T_bs coordinates: Sigma_pp from the band (cov), Sigma_pe the columns ecol .. ecol + 5
+/// of Sigma_pb (cov_pb, np x nb), Sigma_ee that 6 x 6 block of Sigma_bb (cov_bb, nb x nb), all unscaled. ecol < 0: T_bs is not an unknown of
+/// the computed covariance — J = J_s, and for an identity T_bs every operation is k_cov_sample's, in its order. T_bs: seven doubles in device
+/// memory (a row of T.cam or T.sensor, T.imu->T_bs). Lane 0 evaluates the spline and J, the lanes below 6K + 6 own one column of J Sigma_aug
+/// each, the lanes below 36 one entry of the result; one fixed order in every sum, no atomics: two calls are bit-identical.
+template <int K>
+__global__ void __launch_bounds__(kBlock) k_cov_sample_sensor(Tables T, const double* cov, const double* cov_pb, const double* cov_bb, int nb,
+                                                              const double* T_bs, int ecol, int n, const double* stamps, double* out) {
+  constexpr int M = 6 * K + 6;  // row stride of J and of J Sigma_aug
+  __shared__ double Js[kBlock / 64][6 * M];
+  __shared__ double JS[kBlock / 64][6 * M];
+  __shared__ int first_s[kBlock / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, i = blockIdx.x * (kBlock / 64) + w;
+  const bool active = i < n;
+  const int cols = ecol < 0 ? 6 * K : M;
+  double* J = Js[w];
+  if (active && lane == 0) {
+    double u;
+    const int first = segment_of(stamps[i], T.sp.t0, T.sp.dt, K, &u);
+    double lam[K], dl[1], ddl[1];
+    basis_weights<K>(T.basis, u, T.sp.inv_dt, lam, dl, ddl, 0);
+    Quat qw;
+    V3 pw;
+    M3 G[K];
+    spline_pose_jac<K>(T.cp + 8 * first, lam, &qw, &pw, G);
+    const double sensor[7] = {T_bs[0], T_bs[1], T_bs[2], T_bs[3], T_bs[4], T_bs[5], T_bs[6]};
+    const Quat q_bs{sensor[0], sensor[1], sensor[2], sensor[3]}, q_ws = qmul(qw, q_bs);
+    const M3 R_wb = qmat(qw);
+    const V3 lever = mul(R_wb, V3{sensor[4], sensor[5], sensor[6]});
+    // (the measurement is handed over as a value of its own: prior_residual forms conj(q_m) (x) q_ws, and a compiler that knew q_m to BE q_ws
+    //  would contract that product differently from k_cov_sample, where the two are different values — the last bits of an identity sensor)
+    const double meas[7] = {cov_opaque(q_ws.x), cov_opaque(q_ws.y), cov_opaque(q_ws.z), cov_opaque(q_ws.w), lever.x + pw.x, lever.y + pw.y, lever.z + pw.z};
+    double r[6];
+    V3 rot, Rt;
+    M3 R_ws;
+    prior_residual(qw, pw, sensor, meas, r, &rot, &R_ws, &Rt);
+    const So3Coef sc = so3_coef(dot(rot, rot), true);
+    const M3 Jri = rodrigues_poly(rot, 0.5, sc.D);
+    const M3 Arot = mul_nt(Jri, R_ws);
+    const M3 Apos = scale(-1.0, hat(Rt));
+    for (int j = 0; j < K; ++j) {
+      const double Bj = lam[j] - (j + 1 < K ? lam[j + 1] : 0.0);
+      const M3 Jr = scale(2.0, mul(Arot, G[j])), Jp = scale(2.0, mul(Apos, G[j]));
+      for (int a = 0; a < 3; ++a)
+        for (int c = 0; c < 3; ++c) {
+          J[a * M + 6 * j + c] = Jr.m[3 * a + c];
+          J[a * M + 6 * j + 3 + c] = 0.0;
+          J[(3 + a) * M + 6 * j + c] = Jp.m[3 * a + c];
+          J[(3 + a) * M + 6 * j + 3 + c] = a == c ? Bj : 0.0;
+        }
+    }
+    if (ecol >= 0) {
+      const M3 Erot = scale(2.0, mul_nt(Jri, qmat(q_bs)));  // 2 J_r^-1 R_bs^T
+      for (int a = 0; a < 3; ++a)
+        for (int c = 0; c < 3; ++c) {
+          J[a * M + 6 * K + c] = Erot.m[3 * a + c];
+          J[a * M + 6 * K + 3 + c] = 0.0;
+          J[(3 + a) * M + 6 * K + c] = 0.0;
+          J[(3 + a) * M + 6 * K + 3 + c] = R_wb.m[3 * a + c];
+        }
+    }
+    first_s[w] = first;
+  }
+  __syncthreads();
+  const int ncb = 6 * T.bw;
+  if (active && lane < cols) {  // column `lane` of J Sigma_aug
+    const int f6 = 6 * first_s[w];
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    if (lane < 6 * K) {
+      for (int m = 0; m < 6 * K; ++m) {
+        const double s = cov_band_at(cov, ncb, f6 + m, f6 + lane);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) acc[a] = fma(J[a * M + m], s, acc[a]);
+      }
+      if (ecol >= 0) {
+        const double* pe = cov_pb + size_t(f6 + lane) * nb + ecol;  // (row of Sigma_pe: the column of its transpose)
+        for (int m = 0; m < 6; ++m) {
+          const double s = pe[m];
+#pragma unroll
+          for (int a = 0; a < 6; ++a) acc[a] = fma(J[a * M + 6 * K + m], s, acc[a]);
+        }
+      }
+    } else {
+      const int e = ecol + lane - 6 * K;
+      for (int m = 0; m < 6 * K; ++m) {
+        const double s = cov_pb[size_t(f6 + m) * nb + e];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) acc[a] = fma(J[a * M + m], s, acc[a]);
+      }
+      for (int m = 0; m < 6; ++m) {
+        const double s = cov_bb[size_t(ecol + m) * nb + e];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) acc[a] = fma(J[a * M + 6 * K + m], s, acc[a]);
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) JS[w][a * M + lane] = acc[a];
+  }
+  __syncthreads();
+  if (active && lane < 36) {
+    const int a = lane / 6, b = lane % 6;
+    double v = 0.0;
+    for (int c = 0; c < cols; ++c) v = fma(JS[w][a * M + c], J[b * M + c], v);
     out[36 * size_t(i) + lane] = v;
   }
 }

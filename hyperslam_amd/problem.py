@@ -356,8 +356,8 @@ class Problem:
     def covariance(self):
         """What compute_covariance() computed, in Ceres-local coordinates: control_points (n_cp, 6, 6), control_point_band (n_cp, bw, 6, 6) —
         entry [i, j] is the block of control points (i, i + j) —, landmarks (n_lm, 3, 3) in table order, border (nb, nb) (bias splines, gravity,
-        then the free camera coordinates of set_camera_covariance, in the column order of reduced_system) and control_point_border
-        (n_cp, 6, nb), the covariance between each control point and the border unknowns."""
+        then the free IMU coordinates of set_imu_covariance and the free camera coordinates of set_camera_covariance, in the column order of
+        reduced_system) and control_point_border (n_cp, 6, nb), the covariance between each control point and the border unknowns."""
         n_cp, bw = self.window.n_cp, self.lib.band_blocks(self.h)
         n_lm, nb = self.num_landmarks(), self.dim_pose() - 6 * n_cp
         cpb, band = np.zeros((n_cp, 6, 6)), np.zeros((n_cp, bw, 6, 6))
@@ -371,6 +371,17 @@ class Problem:
         st = _arr(stamps, _f64)
         out = np.zeros((len(st), 6, 6))
         self._check(self.lib.sample_covariance(self.h, len(st), _d(st), _d(out)), "sample_covariance")
+        return out
+
+    def sample_sensor_covariance(self, kind, index, stamps):
+        """Covariance (n, 6, 6) of the sensor pose T_wb(t) o T_bs at each stamp, in the coordinates of sample_covariance. kind: HS_SENSOR_CAMERA
+        (index into the camera table), HS_SENSOR_IMU (index 0) or HS_SENSOR_PLAIN (the window's plain sensors). A T_bs that is a free unknown of
+        the computed covariance (set_camera_covariance / set_imu_covariance) contributes its own uncertainty and its correlation with the pose."""
+        if not hasattr(self.lib, "sample_sensor_covariance"):
+            raise HsError(f"{self.lib.prefix}sample_sensor_covariance: not provided by this library")
+        st = _arr(stamps, _f64)
+        out = np.zeros((len(st), 6, 6))
+        self._check(self.lib.sample_sensor_covariance(self.h, int(kind), int(index), len(st), _d(st), _d(out)), "sample_sensor_covariance")
         return out
 
     def solve(self, max_iterations=5):
@@ -412,6 +423,12 @@ class Problem:
                 return  # (off is what a library without the entry point does anyway)
             raise HsError(f"{self.lib.prefix}set_imu_estimation: not provided by this library (sensor blocks are constant there)")
         self._check(self.lib.set_imu_estimation(self.h, int(bool(enabled))), "set_imu_estimation")
+
+    def set_imu_covariance(self, enabled=True):
+        """compute_covariance() takes the free IMU blocks of set_imu_constancy on this handle (off by default: it refuses them)."""
+        if not hasattr(self.lib, "set_imu_covariance"):
+            raise HsError(f"{self.lib.prefix}set_imu_covariance: not provided by this library (sensor blocks are constant there)")
+        self._check(self.lib.set_imu_covariance(self.h, int(bool(enabled))), "set_imu_covariance")
 
     def imu(self):
         """Current IMU parameters: dict(T_bs (7), i_g (6), i_a (6), S_g (9), X_a (9)) in the layout of the window's imu table."""

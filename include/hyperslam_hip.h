@@ -177,13 +177,13 @@ int hs_set_imu(hs_problem* p, const double* T_bs, const double* i_g, const doubl
  * residuals leaves the IMU columns out; a coordinate whose column is zero stays, with 1 on its diagonal. hs_dim_pose and hs_reduced_system
  * (also through the delta interface) BUILD their system; hs_solve estimates the free blocks once hs_set_imu_estimation has enabled it on the
  * handle and by default refuses a handle with a free IMU block (HS_ERR_STATE) whatever hs_set_camera_estimation says. hs_compute_covariance
- * refuses such a handle (HS_ERR_STATE) whatever hs_set_camera_covariance says, and hs_solve / hs_reduced_system refuse a sharded handle
- * (world > 1) with one (HS_ERR_STATE). */
+ * takes the free blocks once hs_set_imu_covariance has enabled it on the handle and by default refuses a handle with one (HS_ERR_STATE)
+ * whatever hs_set_camera_covariance says, and hs_solve / hs_reduced_system refuse a sharded handle (world > 1) with one (HS_ERR_STATE). */
 int hs_set_imu_constancy(hs_problem* p, const uint8_t* constant);
 /* hs_solve estimates the free IMU blocks of hs_set_imu_constancy on this handle (enabled != 0). Off by default: hs_solve then refuses a handle
  * with a free IMU block exactly as before (HS_ERR_STATE), whatever hs_set_camera_estimation says. On: a handle whose free blocks are IMU blocks
  * only is solved; one that has free camera blocks as well needs hs_set_camera_estimation too (otherwise the camera refusal). Still refused:
- * sharded handles (world > 1), a weight matrix, hs_compute_covariance. An accepted step moves the IMU parameters like every other variable:
+ * sharded handles (world > 1), a weight matrix; hs_compute_covariance has a switch of its own (hs_set_imu_covariance). An accepted step moves the IMU parameters like every other variable:
  * hs_get_imu, hs_cost, hs_linearize, hs_reduced_system, a later hs_solve and the delta interface see the estimate, hs_snapshot / hs_restore
  * cover the five blocks, hs_set_imu overrides them (and keeps the flags). Such a window is solved one-ended with the IMU coordinates as border
  * columns; the border (bias / gravity + free IMU coordinates + the free camera coordinates of hs_set_camera_estimation) is limited to 137
@@ -191,6 +191,16 @@ int hs_set_imu_constancy(hs_problem* p, const uint8_t* constant);
  * bias control points (104 bias / gravity unknowns) has room for 33 of the 36 IMU coordinates. Handles without a free IMU coordinate are not
  * affected by the switch; toggling it re-prepares the tables. DESIGN.md section 14. */
 int hs_set_imu_estimation(hs_problem* p, int enabled);
+/* hs_compute_covariance takes the free IMU blocks of hs_set_imu_constancy on this handle (enabled != 0): their coordinates are free border
+ * unknowns of the covariance, behind gravity and in front of the free camera coordinates (the column order of hs_reduced_system). Off by
+ * default: hs_compute_covariance then refuses a handle with a free IMU coordinate exactly as before (HS_ERR_STATE). A switch of its own,
+ * independent of hs_set_imu_estimation and of hs_set_camera_covariance: a handle that has free camera blocks as well needs
+ * hs_set_camera_covariance too (otherwise the camera refusal). The limits of hs_set_imu_estimation (137 border unknowns, 400 control points)
+ * do not apply. T_bs and X_a both free is refused (HS_ERR_NUMERIC): the accelerometer model a_m = a_i + diag(F_a (X_a (+) t_bs)) depends on
+ * the translation of T_bs and on X_a through their sum only, so without damping their columns are exactly dependent (hs_solve, which damps,
+ * estimates both). Toggling it makes a computed covariance stale. Handles without a free IMU coordinate are not affected. DESIGN.md
+ * sections 12 and 14. */
+int hs_set_imu_covariance(hs_problem* p, int enabled);
 /* Current IMU parameters in the layout of hs_set_imu: T_bs[7], i_g[6], i_a[6], S_g[9], X_a[9]. Each pointer may be NULL. HS_ERR_STATE on a
  * handle without an IMU. */
 int hs_get_imu(hs_problem* p, double* T_bs, double* i_g, double* i_a, double* S_g, double* X_a);
@@ -284,12 +294,15 @@ int hs_reduced_system(hs_problem* p, double radius, double* S, double* g);
 /* The covariance is the inverse of the undamped Gauss-Newton matrix J'J at the values the device holds (what hs_get_* return), built as the
  * solver builds it: robustified Jacobians (Ceres' loss corrector), landmarks eliminated by Schur complement, zero LM damping. Coordinates are
  * Ceres-local, the columns of hs_linearize: control points [d_rot(3) d_trans(3)], landmarks Euclidean (3), bias control points R3 each,
- * gravity the 2-dim SphereManifold basis, free camera blocks as in hs_set_camera_constancy; the border unknowns in the column order of
- * hs_reduced_system (bias_g points, bias_a points, gravity, free camera coordinates).
+ * gravity the 2-dim SphereManifold basis, free IMU blocks as in hs_set_imu_constancy, free camera blocks as in hs_set_camera_constancy; the
+ * border unknowns in the column order of hs_reduced_system (bias_g points, bias_a points, gravity, free IMU coordinates, free camera
+ * coordinates).
  * Constant control points / landmarks / bias splines / gravity have zero covariance (as in Ceres). Camera blocks are constant unless
  * hs_set_camera_constancy frees them AND hs_set_camera_covariance is on; a handle with free camera coordinates and the switch off is refused
  * (HS_ERR_STATE). A free camera coordinate without information (the intrinsics of a camera seen through bearing rows only, say) gives
- * HS_ERR_NUMERIC naming "camera <c>, <T_bs|intrinsics|distortion> coordinate <j>".
+ * HS_ERR_NUMERIC naming "camera <c>, <T_bs|intrinsics|distortion> coordinate <j>". IMU blocks likewise: hs_set_imu_constancy AND
+ * hs_set_imu_covariance, HS_ERR_STATE with the switch off, HS_ERR_NUMERIC naming "IMU <T_bs|i_g|i_a|S_g|X_a> coordinate <j>", and
+ * HS_ERR_NUMERIC before any device work for T_bs and X_a both free (hs_set_imu_covariance).
  * A free coordinate without information (a structurally zero column, a non-positive pivot, or a pivot below 1e-12 of its Jacobi-scaled diagonal;
  * per landmark: of its scaled 3x3 block) gives HS_ERR_NUMERIC with a message naming the control point, border unknown or landmark.
  * Fixing the gauge is the caller's business: an almost singular gauge direction is not guaranteed to be caught.
@@ -298,8 +311,9 @@ int hs_reduced_system(hs_problem* p, double radius, double* S, double* g);
 int hs_compute_covariance(hs_problem* p);
 /* cp_blocks n_cp x 6 x 6 (marginals); cp_band n_cp x bw x 6 x 6, entry (i, j) = block (i, i + j) (zero past the last control point,
  * bw = hs_band_blocks); landmarks n_lm x 3 x 3 (table order; NaN for a landmark without residual rows: it is not in the problem);
- * border nb x nb, nb = hs_dim_pose - 6 n_cp: bias_g points, bias_a points, gravity, then the free camera coordinates (with
- * hs_set_camera_covariance) in the column order of hs_reduced_system. Each pointer is nullable. */
+ * border nb x nb, nb = hs_dim_pose - 6 n_cp: bias_g points, bias_a points, gravity, then the free IMU coordinates (with
+ * hs_set_imu_covariance) and the free camera coordinates (with hs_set_camera_covariance) in the column order of hs_reduced_system. Each
+ * pointer is nullable. */
 int hs_get_covariance(hs_problem* p, double* cp_blocks, double* cp_band, double* landmarks, double* border);
 /* cp_border 6 n_cp x nb, row-major: the covariance between the control-point coordinates (rows) and the border unknowns (columns, as in
  * hs_get_covariance). Rows of constant control points and columns of constant border unknowns are zero. HS_ERR_STATE when stale. */
@@ -307,6 +321,17 @@ int hs_get_covariance_cross(hs_problem* p, double* cp_border);
 /* Covariance of the pose at n stamps (n x 6 x 6, the residual coordinates of HS_PRIOR: [Log(R_m' R) ; p - p_m] with the measurement at the
  * pose itself): J(t) Sigma J(t)' over the k control points the pose depends on. HS_ERR_INVALID for a stamp outside the valid range. */
 int hs_sample_covariance(hs_problem* p, int n, const double* stamps, double* cov);
+/* Covariance of the SENSOR pose T_ws(t) = T_wb(t) o T_bs at n stamps (n x 6 x 6, the coordinates of hs_sample_covariance with the measurement
+ * at the sensor pose). kind / index: a camera of hs_set_cameras, the IMU (index 0) or a plain sensor of hs_set_sensors (its T_bs is always
+ * constant). T_bs is the value the device holds (the estimate after an hs_solve). Where the sensor's T_bs is a free unknown of the computed
+ * covariance (hs_set_camera_covariance / hs_set_imu_covariance) its uncertainty and its correlation with the control points enter:
+ * J_s Sigma_pp J_s' + J_s Sigma_pe J_e' + (J_s Sigma_pe J_e')' + J_e Sigma_ee J_e', J_s / J_e the state / extrinsics Jacobians of the pose
+ * prior; otherwise J_s Sigma_pp J_s' alone (for an identity T_bs: hs_sample_covariance bit for bit). HS_ERR_STATE when stale, HS_ERR_INVALID
+ * for a stamp outside the valid range, an unknown kind or an index outside its table. */
+#define HS_SENSOR_CAMERA 0
+#define HS_SENSOR_IMU 1
+#define HS_SENSOR_PLAIN 2
+int hs_sample_sensor_covariance(hs_problem* p, int kind, int index, int n, const double* stamps, double* cov);
 
 /* ---- solve ------------------------------------------------------------------------------------------------------ */
 /* Replaces CeresOptimizer::optimize (optimizer.cpp:276-280) with the options of optimizer.cpp:38-54 (trust-region LM,
