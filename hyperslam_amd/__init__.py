@@ -7,5 +7,6 @@ from ._lib import HS_BEARING, HS_INERTIAL, HS_INERTIAL_AS_REFERENCE, HS_INERTIAL
 from ._lib import (HS_MANIFOLD_BIAS_POINT, HS_MANIFOLD_CONSTANT, HS_MANIFOLD_CONTROL_POINT, HS_MANIFOLD_EUCLIDEAN,  # noqa: F401
                    HS_MANIFOLD_SE3, HS_MANIFOLD_SPHERE3)
 from ._lib import HS_SENSOR_CAMERA, HS_SENSOR_IMU, HS_SENSOR_PLAIN  # noqa: F401
+from ._lib import HS_DISTORTION_EQUIDISTANT, HS_DISTORTION_RADTAN  # noqa: F401
 from .problem import HsError, Problem, Window  # noqa: F401
 from .tracker import Tracker  # noqa: F401

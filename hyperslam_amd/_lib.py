@@ -20,6 +20,7 @@ HS_INERTIAL_AS_REFERENCE, HS_INERTIAL_EXACT = 0, 1  # hs_set_inertial_jacobian
  HS_MANIFOLD_BIAS_POINT) = range(6)
 HS_NO_CONVERGENCE, HS_CONVERGENCE, HS_FAILURE = 0, 1, 2
 HS_SENSOR_CAMERA, HS_SENSOR_IMU, HS_SENSOR_PLAIN = 0, 1, 2  # hs_sample_sensor_covariance
+HS_DISTORTION_RADTAN, HS_DISTORTION_EQUIDISTANT = 0, 1  # hs_set_camera_models
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
@@ -145,6 +146,9 @@ _PRODUCT_ONLY = {
     # marginal covariances (the oracle has no counterpart)
     # free camera blocks (the oracle keeps every sensor block constant)
     "set_camera_constancy": (C.c_int, [C.c_void_p, C.c_int, c_uint8_p]),
+    # distortion model per camera (the oracle knows the radial-tangential model alone)
+    "set_camera_models": (C.c_int, [C.c_void_p, C.c_int, c_int32_p]),
+    "get_camera_models": (C.c_int, [C.c_void_p, c_int32_p]),
     # free IMU blocks (the build of their reduced system, their estimation in hs_solve)
     "set_imu_constancy": (C.c_int, [C.c_void_p, c_uint8_p]),
     "set_imu_estimation": (C.c_int, [C.c_void_p, C.c_int]),

@@ -157,10 +157,43 @@ int hs_set_cameras(hs_problem* p, int n, const double* T_bs, const double* intr,
   for (int i = 0; i < n; ++i) {
     double* c = &p->cam[size_t(kCamStride) * i];
     std::memcpy(c, T_bs + 7 * i, 56), std::memcpy(c + 7, intr + 4 * i, 32), std::memcpy(c + 11, dist + 4 * i, 32);
+    if (same_count && !p->cam_models.empty()) c[15] = double(p->cam_models[i]);  // (slot 15: the distortion model, hs_set_camera_models)
   }
   if (same_count && before == p->cam) return HS_OK;
-  if (!same_count) p->cam_const.clear();  // (constancy flags are per camera: a table of another size starts from the default)
+  if (!same_count) p->cam_const.clear(), p->cam_models.clear();  // (constancy flags and models are per camera: a table of another size starts from the default)
   p->touch(same_count ? unsigned(hs_problem::vCam) : unsigned(hs_problem::vCam | hs_problem::kVis));  // (the visual section checks the camera indices)
+  return HS_OK;
+}
+
+/// The distortion model of every camera (HS_DISTORTION_*): kept on the handle and written into slot 15 of the camera records, where every
+/// kernel that projects or un-projects a pixel reads it (factors.hpp: visual_measure). Re-prepares what hs_set_cameras re-prepares.
+int hs_set_camera_models(hs_problem* p, int n, const int32_t* models) {
+  if (!p) return HS_ERR_INVALID;
+  std::vector<int32_t> m;
+  if (models) {
+    if (n != p->n_cam) HS_FAIL(HS_ERR_INVALID, "hs_set_camera_models: n must equal the camera count of hs_set_cameras");
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+      if (models[i] != HS_DISTORTION_RADTAN && models[i] != HS_DISTORTION_EQUIDISTANT)
+        HS_FAIL(HS_ERR_INVALID, "hs_set_camera_models: unknown distortion model " + std::to_string(models[i]) + " (camera " + std::to_string(i) + ")");
+      any |= models[i] != HS_DISTORTION_RADTAN;
+    }
+    if (any) m.assign(models, models + n);  // (every camera radial-tangential: the default, and the same records)
+  }
+  if (m == p->cam_models) return HS_OK;
+  p->cam_models.swap(m);
+  for (int i = 0; i < p->n_cam; ++i) {
+    const double tag = p->cam_models.empty() ? 0.0 : double(p->cam_models[i]);
+    p->cam[size_t(kCamStride) * i + 15] = tag;
+    if (p->cam_snap.size() == p->cam.size()) p->cam_snap[size_t(kCamStride) * i + 15] = tag;  // (hs_restore brings back values, not models)
+  }
+  p->touch(hs_problem::vCam);
+  return HS_OK;
+}
+
+int hs_get_camera_models(hs_problem* p, int32_t* models) {
+  if (!p || !models) return HS_ERR_INVALID;
+  for (int i = 0; i < p->n_cam; ++i) models[i] = p->cam_models.empty() ? HS_DISTORTION_RADTAN : p->cam_models[i];
   return HS_OK;
 }
 
@@ -1374,6 +1407,9 @@ int hs_cost_function_evaluate(hs_problem* p, int type, int idx, const double* co
   int nres = L.num_residuals;
   if (!rc && (type == HS_PIXEL || type == HS_BEARING)) {
     rc = hs_set_cameras(q, 1, parameters[k], parameters[k + 1], parameters[k + 2]);
+    const int32_t cam_id = type == HS_PIXEL ? p->px_cam[idx] : p->br_cam[idx];
+    const int32_t model = p->cam_models.empty() || cam_id < 0 || cam_id >= p->n_cam ? HS_DISTORTION_RADTAN : p->cam_models[cam_id];
+    if (!rc) rc = hs_set_camera_models(q, 1, &model);  // (the residual's camera keeps its distortion model)
     if (!rc) rc = hs_set_landmarks(q, 1, parameters[k + 3], nullptr);
     stamp = type == HS_PIXEL ? p->px_stamp[idx] : p->br_stamp[idx];
     if (!rc) rc = type == HS_PIXEL ? hs_set_pixel_residuals(q, 1, &stamp, &p->px_meas[2 * idx], &zero, &zero)

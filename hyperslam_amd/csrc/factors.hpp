@@ -29,11 +29,51 @@ struct VisualOut {
   double cost;
 };
 
+/// Equidistant (fisheye, order 4) distortion of the plane point n = (x, y) with coefficients k[0..3] (a convention of this
+/// project):   rho = |n|, theta = atan(rho), t = theta^2,   s = theta (1 + k1 t + k2 t^2 + k3 t^3 + k4 t^4),   d(n) = c n with c = s / rho,
+///   dd/dn = c I + e n n',  e = (s' / (1 + rho^2) - c) / rho^2,  s' = 1 + 3 k1 t + 5 k2 t^2 + 7 k3 t^3 + 9 k4 t^4,
+///   dd/dk_i = theta^(2i+1) / rho n.   At rho = 0: c = 1, e = 0 (n n' is zero there), dd/dk = 0.
+struct Equidistant {
+  double c, e;
+  double theta, irho;  // irho = 1 / rho (0 at rho = 0): dd/dk_i = theta^(2i+1) irho n
+};
+HSD Equidistant equidistant(double x, double y, const double* k) {
+  const double rho2 = x * x + y * y;
+  const double rho = sqrt(rho2);
+  Equidistant o;
+  if (rho == 0.0) {
+    o.c = 1.0, o.e = 0.0, o.theta = 0.0, o.irho = 0.0;
+    return o;
+  }
+  const double theta = atan(rho), t = theta * theta;
+  const double t2 = t * t, t3 = t2 * t, t4 = t2 * t2;
+  const double s = theta * (1.0 + k[0] * t + k[1] * t2 + k[2] * t3 + k[3] * t4);
+  const double sp = 1.0 + 3.0 * k[0] * t + 5.0 * k[1] * t2 + 7.0 * k[2] * t3 + 9.0 * k[3] * t4;
+  o.c = s / rho;
+  o.e = (sp / (1.0 + rho2) - o.c) / rho2;
+  o.theta = theta, o.irho = 1.0 / rho;
+  return o;
+}
+
 /// Projection chain of one visual residual given the sensor-frame point: residual rows and d r / d p_s (2 x 3).
-/// type 0: pixel (pixel.cpp:86-99 ProjectToPlane -> radtan distort -> denormalize; CartesianMetric),
-/// type 1: bearing (bearing.cpp:77 returns p_s; AngularMetric atan2(|p x b|, p . b), second row unused).
+/// type 0: pixel (pixel.cpp:86-99 ProjectToPlane -> distort -> denormalize; CartesianMetric). The distortion model is the camera's tag
+///         cam[15] (HS_DISTORTION_*): 0 radial-tangential, 1 equidistant. The tag is uniform per camera, so a wave mostly takes one side;
+/// type 1: bearing (bearing.cpp:77 returns p_s; AngularMetric atan2(|p x b|, p . b), second row unused; the tag plays no part).
 HSD void visual_measure(int type, V3 ps, const double* cam, const double* meas, bool jac, double* r, double* Jps) {
-  if (type == 0) {
+  if (type == 0 && cam[15] != 0.0) {
+    const double cx = cam[7], cy = cam[8], fx = cam[9], fy = cam[10];
+    const double iz = 1.0 / ps.z;
+    const double x = ps.x * iz, y = ps.y * iz;
+    const Equidistant m = equidistant(x, y, cam + 11);
+    r[0] = cx + fx * (m.c * x) - meas[0];
+    r[1] = cy + fy * (m.c * y) - meas[1];
+    if (jac) {
+      const double d00 = fx * (m.c + m.e * x * x), d01 = fx * (m.e * x * y);
+      const double d10 = fy * (m.e * x * y), d11 = fy * (m.c + m.e * y * y);
+      Jps[0] = d00 * iz, Jps[1] = d01 * iz, Jps[2] = -(d00 * x + d01 * y) * iz;
+      Jps[3] = d10 * iz, Jps[4] = d11 * iz, Jps[5] = -(d10 * x + d11 * y) * iz;
+    }
+  } else if (type == 0) {
     const double cx = cam[7], cy = cam[8], fx = cam[9], fy = cam[10];
     const double k1 = cam[11], k2 = cam[12], p1 = cam[13], p2 = cam[14];
     const double iz = 1.0 / ps.z;
@@ -112,7 +152,7 @@ HSD double visual_cost(const Tables& T, const double* cps, const double* lms, in
 struct VisualIn {
   double stamp, meas[3];
   int type, first;
-  const double* cam;  // 16 doubles: T_bs(7) | cx cy fx fy | k1 k2 p1 p2
+  const double* cam;  // 16 doubles: T_bs(7) | cx cy fx fy | k1 k2 p1 p2 (equidistant: k1 .. k4) | distortion model
   double lm[3];       // landmark position
 };
 HSD VisualIn visual_input(const Tables& T, int q, const double* lms) {

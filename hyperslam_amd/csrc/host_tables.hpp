@@ -234,6 +234,7 @@ struct hs_problem {
   int n_cam = 0;
   std::vector<double> cam;  // n x 16
   std::vector<uint8_t> cam_const;  // hs_set_camera_constancy: n x 3 [T_bs, intrinsics, distortion]; empty: every block constant (camera.hpp:18)
+  std::vector<int32_t> cam_models; // hs_set_camera_models: HS_DISTORTION_* per camera, mirrored in slot 15 of `cam`; empty: every camera radial-tangential
   bool cam_estimation = false;     // hs_set_camera_estimation: hs_solve estimates the free blocks (off: it refuses a handle that has one)
   bool cam_covariance = false;     // hs_set_camera_covariance: hs_compute_covariance takes the free blocks (off: it refuses a handle that has one)
   std::vector<double> cam_snap;    // hs_snapshot: the camera table (host copy; hs_solve keeps `cam` equal to the device table)

@@ -25,10 +25,26 @@ __global__ void __launch_bounds__(kBlock) k_sample_trajectory(Tables T, int n, c
   if (acc) acc[6 * i] = S.al.x, acc[6 * i + 1] = S.al.y, acc[6 * i + 2] = S.al.z, acc[6 * i + 3] = S.a.x, acc[6 * i + 4] = S.a.y, acc[6 * i + 5] = S.a.z;
 }
 
-/// Pixel -> unit bearing in the sensor frame (radtan undistortion by fixed-point iteration; cam = [T_bs(7) | cx cy fx fy | k1 k2 p1 p2]).
+/// Pixel -> unit bearing in the sensor frame; cam = [T_bs(7) | cx cy fx fy | k1 k2 p1 p2 | distortion model]. Radtan: undistortion by
+/// fixed-point iteration. Equidistant (cam[15] != 0, coefficients k1 .. k4): s(theta) = rho_d by ten Newton steps from theta = rho_d, the
+/// bearing is (sin(theta) n_d / rho_d, cos(theta)) and the optical axis at rho_d = 0.
 HSD V3 pixel_to_bearing(const double* cam, double u, double v) {
   const double xd = (u - cam[7]) / cam[9], yd = (v - cam[8]) / cam[10];
   const double k1 = cam[11], k2 = cam[12], p1 = cam[13], p2 = cam[14];
+  if (cam[15] != 0.0) {
+    const double rho_d = sqrt(xd * xd + yd * yd);
+    if (rho_d == 0.0) return V3{0.0, 0.0, 1.0};
+    const double k3 = p1, k4 = p2;
+    double theta = rho_d;
+    for (int it = 0; it < 10; ++it) {
+      const double t = theta * theta, t2 = t * t, t3 = t2 * t, t4 = t2 * t2;
+      const double s = theta * (1.0 + k1 * t + k2 * t2 + k3 * t3 + k4 * t4);
+      const double sp = 1.0 + 3.0 * k1 * t + 5.0 * k2 * t2 + 7.0 * k3 * t3 + 9.0 * k4 * t4;
+      theta -= (s - rho_d) / sp;
+    }
+    const double w = sin(theta) / rho_d;
+    return V3{w * xd, w * yd, cos(theta)};
+  }
   double x = xd, y = yd;
   for (int it = 0; it < 20; ++it) {
     const double r2 = x * x + y * y, rad = 1 + k1 * r2 + k2 * r2 * r2;

@@ -55,7 +55,18 @@ HSD void visual_sensor_jacobians(const Tables& T, const double* cps, int q, bool
     }
 #pragma unroll
   for (int c = 0; c < 16; ++c) rec[12 + c] = 0.0;
-  if (type == 0) {  // pixel.cpp:91-135: denormalize [cx cy fx fy] and radtan [k1 k2 p1 p2] parameter Jacobians
+  if (type == 0 && cam[15] != 0.0) {  // equidistant camera (factors.hpp: equidistant): d = c n, dd/dk_i = theta^(2i+1) / rho n
+    const double fx = cam[9], fy = cam[10];
+    const double iz = 1.0 / ps.z, x = ps.x * iz, y = ps.y * iz;
+    const Equidistant m = equidistant(x, y, cam + 11);
+    double* Ji = rec + 12;
+    double* Jd = rec + 20;
+    Ji[0] = sr, Ji[2] = sr * (m.c * x), Ji[4 + 1] = sr, Ji[4 + 3] = sr * (m.c * y);
+    const double t = m.theta * m.theta;
+    double w = m.theta * t * m.irho;  // theta^3 / rho
+#pragma unroll
+    for (int i = 0; i < 4; ++i, w *= t) Jd[i] = sr * fx * x * w, Jd[4 + i] = sr * fy * y * w;
+  } else if (type == 0) {  // pixel.cpp:91-135: denormalize [cx cy fx fy] and radtan [k1 k2 p1 p2] parameter Jacobians
     const double fx = cam[9], fy = cam[10];
     const double k1 = cam[11], k2 = cam[12], p1 = cam[13], p2 = cam[14];
     const double iz = 1.0 / ps.z, x = ps.x * iz, y = ps.y * iz;

@@ -29,6 +29,7 @@
 
 #ifndef HS_ABI_PREFIX
 #define HS_ABI_PREFIX hs_
+#define HS_HOST_CAMERA_MODELS 1  // the product library: per-camera distortion models (hs_set_camera_models); the oracle, under its own prefix, has none
 #endif
 #define HS_CAT2(a, b) a##b
 #define HS_CAT(a, b) HS_CAT2(a, b)
@@ -404,6 +405,7 @@ class Optimizer {
     if (!delta_)
       t.upload<&HSF(set_spline), &HSF(set_cameras), &HSF(set_sensors), &HSF(set_landmarks), &HSF(set_imu), &HSF(set_gravity), &HSF(set_bearing_residuals),
                &HSF(set_pixel_residuals), &HSF(set_prior_residuals), &HSF(set_inertial_residuals)>(handle_, [&](int rc, const char* what) { check(rc, what); });
+    if (!delta_) applyCameraModels();
     if (num_observations_ == 0 && inertials_.empty() && priors_.empty()) return;  // nothing to optimise yet
     if (before_solve) before_solve(t, num_optimizations_);
     const auto wall1 = std::chrono::steady_clock::now();
@@ -654,6 +656,22 @@ class Optimizer {
       std::copy(cameras_[c].distortion.begin(), cameras_[c].distortion.end(), &D[4 * c]);
     }
     check(HSF(set_cameras)(handle_, int(cameras_.size()), T.data(), I.data(), D.data()), "set_cameras");
+    applyCameraModels();
+  }
+  /// Distortion model of every camera (HS_DISTORTION_*, one per camera of the constructor; empty: radial-tangential, the default). The models
+  /// belong to the library handle, which keeps them over every later camera upload of the same count; they are sent with the next camera upload. A
+  /// library without the entry point (the oracle) takes the default alone.
+  void setCameraModels(const std::vector<int32_t>& models) {
+    if (!models.empty() && models.size() != cameras_.size()) throw std::runtime_error("setCameraModels: one model per camera");
+    camera_models_ = models;
+  }
+  void applyCameraModels() {
+#ifdef HS_HOST_CAMERA_MODELS
+    check(hs_set_camera_models(handle_, int(camera_models_.size()), camera_models_.empty() ? nullptr : camera_models_.data()), "set_camera_models");
+#else
+    if (std::any_of(camera_models_.begin(), camera_models_.end(), [](int32_t m) { return m != HS_DISTORTION_RADTAN; }))
+      throw std::runtime_error("setCameraModels: this library knows the radial-tangential model alone");
+#endif
   }
   void process(const InertialMeasurement& m, Stamp stamp) {  // abstract.cpp:272-292
     InertialMeasurement c = m;
@@ -738,6 +756,7 @@ class Optimizer {
 
   Options opt_;
   std::vector<Camera> cameras_;
+  std::vector<int32_t> camera_models_;  // setCameraModels (empty: every camera radial-tangential)
   bool has_imu_ = false;
   IMU imu_;
   hs_problem* handle_ = nullptr;

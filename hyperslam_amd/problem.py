@@ -50,6 +50,7 @@ class Window:
     cam_intrinsics: np.ndarray = field(default_factory=lambda: np.zeros((0, 4)))
     cam_distortion: np.ndarray = field(default_factory=lambda: np.zeros((0, 4)))
     cam_constant: np.ndarray | None = None  # n_cam x 3 [T_bs, intrinsics, distortion], non-zero = constant; None: every block constant
+    cam_models: np.ndarray | None = None  # n_cam distortion models (HS_DISTORTION_*); None: every camera radial-tangential
     sensor_T_bs: np.ndarray = field(default_factory=lambda: np.zeros((0, 7)))
     landmarks: np.ndarray = field(default_factory=lambda: np.zeros((0, 3)))
     landmark_constant: np.ndarray | None = None
@@ -142,6 +143,7 @@ class Problem:
             self.set_camera_constancy(w.cam_constant)
         elif w.cam_constant is not None and np.any(np.asarray(w.cam_constant) == 0):
             raise HsError(f"{L.prefix}set_camera_constancy: not provided by this library (sensor blocks are constant there)")
+        self.set_camera_models(w.cam_models)  # (None: every camera radial-tangential)
         S = _arr(w.sensor_T_bs, _f64, (-1, 7))
         self._check(L.set_sensors(h, S.shape[0], _d(S)), "set_sensors")
         lm = _arr(w.landmarks, _f64, (-1, 3))
@@ -405,6 +407,26 @@ class Problem:
             return
         c = _arr(constant, np.uint8, (-1, 3))
         self._check(self.lib.set_camera_constancy(self.h, c.shape[0], _u8(c)), "set_camera_constancy")
+
+    def set_camera_models(self, models):
+        """The distortion model of every camera: n_cam values HS_DISTORTION_RADTAN | HS_DISTORTION_EQUIDISTANT; None = radial-tangential (the
+        default). A library without the entry point knows the default alone and raises for anything else."""
+        if not hasattr(self.lib, "set_camera_models"):
+            if models is None or not np.any(np.asarray(models)):
+                return
+            raise HsError(f"{self.lib.prefix}set_camera_models: not provided by this library (its cameras are radial-tangential)")
+        if models is None:
+            self._check(self.lib.set_camera_models(self.h, 0, None), "set_camera_models")
+            return
+        m = _arr(models, np.int32, (-1,))
+        self._check(self.lib.set_camera_models(self.h, m.shape[0], _i(m)), "set_camera_models")
+
+    def camera_models(self):
+        """The distortion model of every camera (n_cam values HS_DISTORTION_*)."""
+        m = np.zeros(len(_arr(self.window.cam_T_bs, _f64, (-1, 7))), np.int32)
+        if hasattr(self.lib, "get_camera_models") and len(m):
+            self._check(self.lib.get_camera_models(self.h, _i(m)), "get_camera_models")
+        return m
 
     def set_imu_constancy(self, constant):
         """Which IMU blocks stay constant: 5 flags [T_bs, i_g, i_a, S_g, X_a], non-zero = constant; None = all (the default)."""

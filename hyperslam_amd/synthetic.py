@@ -112,6 +112,32 @@ def project_radtan(p_s, intr, dist):
     return np.stack([cx + fx * xd, cy + fy * yd], -1)
 
 
+def equidistant_scale(rho, dist):
+    """c(rho) = s(theta) / rho of the equidistant model: theta = atan(rho), s = theta (1 + k1 t + k2 t^2 + k3 t^3 + k4 t^4),
+    t = theta^2; c = 1 at rho = 0."""
+    k1, k2, k3, k4 = np.moveaxis(np.asarray(dist, float), -1, 0)
+    rho = np.asarray(rho, float)
+    theta = np.arctan(rho)
+    t = theta * theta
+    s = theta * (1 + k1 * t + k2 * t ** 2 + k3 * t ** 3 + k4 * t ** 4)
+    zero = rho == 0
+    return np.where(zero, 1.0, s / np.where(zero, 1.0, rho))
+
+
+def project_equidistant(p_s, intr, dist):
+    """Pixel of the sensor-frame point p_s through an equidistant (fisheye) camera, dist = [k1 k2 k3 k4]."""
+    x, y = p_s[..., 0] / p_s[..., 2], p_s[..., 1] / p_s[..., 2]
+    cx, cy, fx, fy = np.moveaxis(intr, -1, 0)
+    c = equidistant_scale(np.sqrt(x * x + y * y), dist)
+    return np.stack([cx + fx * (c * x), cy + fy * (c * y)], -1)
+
+
+def project(p_s, intr, dist, model):
+    """Pixel of p_s through a camera of distortion model `model` (0 radial-tangential, 1 equidistant), row by row."""
+    model = np.broadcast_to(np.asarray(model), p_s.shape[:-1])
+    return np.where((model != 0)[..., None], project_equidistant(p_s, intr, dist), project_radtan(p_s, intr, dist))
+
+
 def make_control_points(rng, order, dt, n_cp, noise=1e-2):
     """Control points at t_j = (j - (k-1)//2) dt (bootstrap rule, abstract.cpp:89) = GT sampled at the knots + tangent noise."""
     t0 = -((order - 1) // 2) * dt
@@ -123,18 +149,25 @@ def make_control_points(rng, order, dt, n_cp, noise=1e-2):
     return t0, cp
 
 
-def _visual_window(seed, order, n_cp, n_lm, obs_pairs, bearing=False, dt=0.1, pixel_noise=0.5, lm_noise=0.05, span=1.0):
+def _visual_window(seed, order, n_cp, n_lm, obs_pairs, bearing=False, dt=0.1, pixel_noise=0.5, lm_noise=0.05, span=1.0, cameras=None):
+    """cameras (optional): dict(models (2,), intrinsics (2, 4), distortion (2, 4), image (width, height)) — the stereo pair keeps the EuRoC
+    extrinsics, the pixels are synthesised through each camera's own model, the anchor pixels are drawn over `image`. None: the EuRoC
+    radial-tangential pair on 752 x 480, as ever (same draws, same window)."""
     rng = SplitMix64(seed)
     t0, cp = make_control_points(rng, order, dt, n_cp)
-    w = Window(order=order, t0=t0, dt=dt, control_points=cp, cam_T_bs=EUROC_CAM_T_BS.copy(), cam_intrinsics=EUROC_CAM_INTRINSICS.copy(),
-               cam_distortion=EUROC_CAM_DISTORTION.copy())
+    intr, dist, models, image = EUROC_CAM_INTRINSICS, EUROC_CAM_DISTORTION, None, (752.0, 480.0)
+    if cameras is not None:
+        intr, dist = np.asarray(cameras["intrinsics"], float).reshape(2, 4), np.asarray(cameras["distortion"], float).reshape(2, 4)
+        models, image = np.asarray(cameras["models"], np.int32).reshape(2), tuple(float(v) for v in cameras.get("image", image))
+    w = Window(order=order, t0=t0, dt=dt, control_points=cp, cam_T_bs=EUROC_CAM_T_BS.copy(), cam_intrinsics=intr.copy(),
+               cam_distortion=dist.copy(), cam_models=None if models is None else models.copy())
     lo, hi = w.valid_range()
     eps = 1e-9
     # landmarks: anchor stamp, pixel in cam0, depth -> back-projected through the ground truth
     ta = rng.uniform(n_lm, lo=lo, hi=hi - eps)
-    px = np.stack([rng.uniform(n_lm, lo=0.0, hi=752.0), rng.uniform(n_lm, lo=0.0, hi=480.0)], -1)
+    px = np.stack([rng.uniform(n_lm, lo=0.0, hi=image[0]), rng.uniform(n_lm, lo=0.0, hi=image[1])], -1)
     depth = rng.uniform(n_lm, lo=2.0, hi=10.0)
-    cx, cy, fx, fy = EUROC_CAM_INTRINSICS[0]
+    cx, cy, fx, fy = intr[0]
     ps = np.stack([(px[:, 0] - cx) / fx * depth, (px[:, 1] - cy) / fy * depth, depth], -1)
     qa, pa = gt_pose(ta)
     q_ws, p_ws = compose(qa, pa, np.broadcast_to(EUROC_CAM_T_BS[0, :4], (n_lm, 4)), np.broadcast_to(EUROC_CAM_T_BS[0, 4:], (n_lm, 3)))
@@ -164,7 +197,8 @@ def _visual_window(seed, order, n_cp, n_lm, obs_pairs, bearing=False, dt=0.1, pi
         b /= np.linalg.norm(b, axis=-1, keepdims=True)
         w.bearing_stamps, w.bearings, w.bearing_landmark, w.bearing_camera = stf, b, lmf, camf
     else:
-        meas = project_radtan(p_s, EUROC_CAM_INTRINSICS[camf], EUROC_CAM_DISTORTION[camf]) + rng.normal(n_obs, 2, sigma=pixel_noise)
+        ideal = project_radtan(p_s, intr[camf], dist[camf]) if models is None else project(p_s, intr[camf], dist[camf], models[camf])
+        meas = ideal + rng.normal(n_obs, 2, sigma=pixel_noise)
         w.pixel_stamps, w.pixels, w.pixel_landmark, w.pixel_camera = stf, meas, lmf, camf
     w.landmarks = lm_gt + rng.normal(n_lm, 3, sigma=lm_noise)
     return w, rng
@@ -188,9 +222,9 @@ def config0(n_cp=32, n_prior=1000):
     return w
 
 
-def config1(n_cp=128, n_landmarks=5000, obs_pairs=5, bearing=False):
+def config1(n_cp=128, n_landmarks=5000, obs_pairs=5, bearing=False, cameras=None):
     """configs[1]: order-4 spline, 128 control points, 50k visual reprojection residuals + 5k landmarks."""
-    w, _ = _visual_window(SEED ^ 1, 4, n_cp, n_landmarks, obs_pairs, bearing=bearing)
+    w, _ = _visual_window(SEED ^ 1, 4, n_cp, n_landmarks, obs_pairs, bearing=bearing, cameras=cameras)
     return w
 
 
@@ -200,9 +234,10 @@ def config3(n_cp=512, n_landmarks=20000, obs_pairs=5):
     return w
 
 
-def small_visual(order=4, n_cp=16, n_landmarks=40, obs_pairs=3, bearing=False, seed=7, with_priors=0, span=1.0):
-    """Small window for oracle-sized parity tests (`span` = seconds a landmark's observations are spread over)."""
-    w, rng = _visual_window(SEED ^ (0x100 + seed), order, n_cp, n_landmarks, obs_pairs, bearing=bearing, span=span)
+def small_visual(order=4, n_cp=16, n_landmarks=40, obs_pairs=3, bearing=False, seed=7, with_priors=0, span=1.0, cameras=None):
+    """Small window for oracle-sized parity tests (`span` = seconds a landmark's observations are spread over; `cameras`: per-camera
+    distortion models and parameters, see _visual_window)."""
+    w, rng = _visual_window(SEED ^ (0x100 + seed), order, n_cp, n_landmarks, obs_pairs, bearing=bearing, span=span, cameras=cameras)
     if with_priors:
         lo, hi = w.valid_range()
         q_bs = quat_exp(rng.uniform(1, 3, lo=-0.5, hi=0.5))
@@ -268,8 +303,8 @@ def config2(n_cp=128, n_landmarks=5000, obs_pairs=5, n_inertial=10000):
     return add_imu(w, rng, n_inertial)
 
 
-def small_inertial(order=4, n_cp=16, n_landmarks=30, obs_pairs=3, n_inertial=80, seed=21, identity=False):
-    w, rng = _visual_window(SEED ^ (0x200 + seed), order, n_cp, n_landmarks, obs_pairs)
+def small_inertial(order=4, n_cp=16, n_landmarks=30, obs_pairs=3, n_inertial=80, seed=21, identity=False, cameras=None):
+    w, rng = _visual_window(SEED ^ (0x200 + seed), order, n_cp, n_landmarks, obs_pairs, cameras=cameras)
     return add_imu(w, rng, n_inertial, identity=identity)
 
 

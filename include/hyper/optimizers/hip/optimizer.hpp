@@ -111,6 +111,15 @@ class Optimizer<kOptimizerSuiteHIP> final : public AbstractOptimizer {
     translation_constant_ = translation_constant;
   }
 
+  /// Distortion model of every camera in the order the sensors were registered (HS_DISTORTION_RADTAN | HS_DISTORTION_EQUIDISTANT; empty:
+  /// radial-tangential, the default). What the four distortion doubles of a Camera mean is NOT detected from the reference's distortion
+  /// type — that is an EXTERNAL header — so a caller with equidistant (Kalibr pinhole-equi, OpenCV fisheye) cameras says so here; without
+  /// this call their coefficients are read as [k1 k2 p1 p2]. Applied with the cameras at the next optimize().
+  auto setCameraModels(const std::vector<std::int32_t>& models) -> void {
+    CHECK(models.empty() || models.size() == cameras_.size()) << "one distortion model per camera";
+    camera_models_ = models;
+  }
+
   /// cc:189-232. A residual block keeps its landmark's parameter block alive in Ceres (AddResidualBlock registers an unknown block): an
   /// observation of a landmark that was retired earlier (addLandmark is only called for NEW landmarks, abstract.cpp:252-257) makes
   /// it active again, like there.
@@ -223,6 +232,8 @@ class Optimizer<kOptimizerSuiteHIP> final : public AbstractOptimizer {
       std::copy_n(parameters[Traits<Camera>::kDistortionOffset]->asVector().data(), 4, &cam_d[4 * c]);
     }
     check(hs_set_cameras(handle_, static_cast<int>(cameras_.size()), cam_T.data(), cam_i.data(), cam_d.data()));
+    if (camera_models_.empty() || camera_models_.size() == cameras_.size())  // (the handle keeps them over uploads of the same camera count)
+      check(hs_set_camera_models(handle_, static_cast<int>(camera_models_.size()), camera_models_.empty() ? nullptr : camera_models_.data()));
     std::vector<double> sensor_T(7 * pose_sensors_.size());
     for (std::size_t s = 0; s < pose_sensors_.size(); ++s) std::copy_n(pose_sensors_[s]->parameters()[0]->asVector().data(), 7, &sensor_T[7 * s]);
     check(hs_set_sensors(handle_, static_cast<int>(pose_sensors_.size()), sensor_T.data()));
@@ -486,6 +497,7 @@ class Optimizer<kOptimizerSuiteHIP> final : public AbstractOptimizer {
 
   hs_problem* handle_{nullptr};
   std::vector<const Camera*> cameras_;
+  std::vector<std::int32_t> camera_models_;  // setCameraModels (empty: every camera radial-tangential)
   std::vector<const Sensor*> pose_sensors_;
   std::unordered_map<const Sensor*, std::int32_t> camera_index_, pose_sensor_index_;
   IMU* imu_{nullptr};

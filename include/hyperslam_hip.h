@@ -128,6 +128,21 @@ int hs_set_spline(hs_problem* p, int order, double t0, double dt, int n_cp, cons
 /* Replaces setSensorManifold for cameras (optimizer.cpp:143-155; constant blocks, camera.hpp:18).
  * T_bs n x 7, intrinsics n x 4 [cx cy fx fy] (settings.yaml:38-40), distortion n x 4 radtan [k1 k2 p1 p2] (:42-45). */
 int hs_set_cameras(hs_problem* p, int n, const double* T_bs, const double* intrinsics, const double* distortion);
+/* Distortion model per camera: what the four distortion doubles of hs_set_cameras mean wherever a pixel is projected or un-projected
+ * (pixel residuals in hs_linearize, hs_cost, hs_cost_function_evaluate, hs_reduced_system, hs_solve, hs_compute_covariance; the pixels of
+ * hs_process_tracks). Bearing residuals ignore it, as they ignore intrinsics. Both models act on the plane point n = (x, y) / z, z > 0.
+ *   HS_DISTORTION_RADTAN       [k1 k2 p1 p2], the default (settings.yaml:42-45)
+ *   HS_DISTORTION_EQUIDISTANT  [k1 k2 k3 k4] (Kalibr pinhole-equi, OpenCV fisheye), order 4:
+ *       theta = atan(|n|), d(n) = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8) n / |n|        
+ * models: n values, n = the camera count of hs_set_cameras; NULL (or all zeros) restores the default. An unknown value or another n is
+ * HS_ERR_INVALID. The models belong to the handle like the constancy flags: hs_set_cameras with the same count keeps them, a camera table of
+ * another size resets them. Cameras of different models may share a handle. hs_snapshot / hs_restore, the delta interface and camera
+ * estimation leave them as they are. */
+#define HS_DISTORTION_RADTAN 0
+#define HS_DISTORTION_EQUIDISTANT 1
+int hs_set_camera_models(hs_problem* p, int n, const int32_t* models);
+/* The model of every camera of hs_set_cameras (n values). */
+int hs_get_camera_models(hs_problem* p, int32_t* models);
 /* Camera blocks the solver may estimate (Manifold<Sensor>::setTransformationConstant, Manifold<Camera>::setIntrinsicsConstant /
  * setDistortionConstant). constant: n x 3 flags [transformation, intrinsics, distortion] per camera, n = the camera count of
  * hs_set_cameras; non-zero keeps the block constant. NULL restores the default: every block constant (camera.hpp:18). A camera table of
