@@ -159,9 +159,9 @@ int hs_set_cameras(hs_problem* p, int n, const double* T_bs, const double* intr,
     std::memcpy(c, T_bs + 7 * i, 56), std::memcpy(c + 7, intr + 4 * i, 32), std::memcpy(c + 11, dist + 4 * i, 32);
     if (same_count && !p->cam_models.empty()) c[15] = double(p->cam_models[i]);  // (slot 15: the distortion model, hs_set_camera_models)
   }
-  if (same_count && before == p->cam) return HS_OK;
+  if (same_count && before == p->cam && !(p->ahead & hs_problem::vCam)) return HS_OK;  // (nothing to send: the device holds exactly this table)
   if (!same_count) p->cam_const.clear(), p->cam_models.clear();  // (constancy flags and models are per camera: a table of another size starts from the default)
-  p->touch(same_count ? unsigned(hs_problem::vCam) : unsigned(hs_problem::vCam | hs_problem::kVis));  // (the visual section checks the camera indices)
+  p->touch(same_count ? unsigned(hs_problem::vCam) : unsigned(hs_problem::vCam | hs_problem::kVis), hs_problem::vCam);  // (the visual section checks the camera indices)
   return HS_OK;
 }
 
@@ -181,11 +181,16 @@ int hs_set_camera_models(hs_problem* p, int n, const int32_t* models) {
     if (any) m.assign(models, models + n);  // (every camera radial-tangential: the default, and the same records)
   }
   if (m == p->cam_models) return HS_OK;
+  if (const int rc = fetch(p, hs_problem::vCam)) return rc;  // (the values next to the tags are the device's)
   p->cam_models.swap(m);
+  std::vector<double> tags(p->n_cam, 0.0);
   for (int i = 0; i < p->n_cam; ++i) {
-    const double tag = p->cam_models.empty() ? 0.0 : double(p->cam_models[i]);
-    p->cam[size_t(kCamStride) * i + 15] = tag;
-    if (p->cam_snap.size() == p->cam.size()) p->cam_snap[size_t(kCamStride) * i + 15] = tag;  // (hs_restore brings back values, not models)
+    if (!p->cam_models.empty()) tags[i] = double(p->cam_models[i]);
+    p->cam[size_t(kCamStride) * i + 15] = tags[i];
+  }
+  if (p->has_snapshot && p->n_cam && p->d_cam_snap.cap >= p->cam.size()) {  // hs_restore brings back values, not models: the snapshot's tags follow
+    HIP_TRY(hipMemcpy2DAsync(p->d_cam_snap.p + 15, kCamStride * 8, tags.data(), 8, 8, p->n_cam, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));  // (`tags` is leaving)
   }
   p->touch(hs_problem::vCam);
   return HS_OK;
@@ -236,6 +241,7 @@ int hs_set_camera_covariance(hs_problem* p, int enabled) {
 
 int hs_get_cameras(hs_problem* p, double* T_bs, double* intr, double* dist) {
   if (!p) return HS_ERR_INVALID;
+  if (const int rc = fetch(p, hs_problem::vCam)) return rc;
   for (int i = 0; i < p->n_cam; ++i) {
     const double* c = &p->cam[size_t(kCamStride) * i];
     if (T_bs) std::memcpy(T_bs + 7 * i, c, 56);
@@ -279,13 +285,14 @@ int hs_set_imu(hs_problem* p, const double* T_bs, const double* i_g, const doubl
   const bool same_structure = p->has_imu && p->kb == bias_order && p->bias_t0 == bias_t0 && p->bias_dt == bias_dt && p->n_bias == n_bias &&
                               p->bias_const == (bias_constant != 0);
   p->has_imu = true;
-  std::memcpy(p->imu_T_bs, T_bs, 56), std::memcpy(p->imu_i_g, i_g, 48), std::memcpy(p->imu_i_a, i_a, 48);
-  std::memcpy(p->imu_S_g, S_g, 72), std::memcpy(p->imu_X_a, X_a, 72);
+  ImuParams& ip = p->imu;
+  std::memcpy(ip.T_bs, T_bs, sizeof ip.T_bs), std::memcpy(ip.i_g, i_g, sizeof ip.i_g), std::memcpy(ip.i_a, i_a, sizeof ip.i_a);
+  std::memcpy(ip.S_g, S_g, sizeof ip.S_g), std::memcpy(ip.X_a, X_a, sizeof ip.X_a);
   p->kb = bias_order, p->bias_t0 = bias_t0, p->bias_dt = bias_dt, p->n_bias = n_bias;
   p->bias_g.assign(bias_g, bias_g + size_t(4) * n_bias), p->bias_a.assign(bias_a, bias_a + size_t(4) * n_bias);
   p->bias_const = bias_constant != 0;
   // (new bias knots: the inertial records index them, the border of the reduced system changes size)
-  p->touch(same_structure ? unsigned(hs_problem::vImu | hs_problem::vBias) : unsigned(hs_problem::vImu | hs_problem::vBias | hs_problem::kIne | hs_problem::kTail), hs_problem::vBias);
+  p->touch(same_structure ? unsigned(hs_problem::vImu | hs_problem::vBias) : unsigned(hs_problem::vImu | hs_problem::vBias | hs_problem::kIne | hs_problem::kTail), hs_problem::vImu | hs_problem::vBias);
   return HS_OK;
 }
 
@@ -329,27 +336,17 @@ int hs_set_imu_covariance(hs_problem* p, int enabled) {
   return HS_OK;
 }
 
-/// The host copies: hs_solve keeps them equal to the device's parameters.
 int hs_get_imu(hs_problem* p, double* T_bs, double* i_g, double* i_a, double* S_g, double* X_a) {
   if (!p) return HS_ERR_INVALID;
   if (!p->has_imu) HS_FAIL(HS_ERR_STATE, "hs_get_imu: no IMU (hs_set_imu has not been called)");
-  if (T_bs) std::memcpy(T_bs, p->imu_T_bs, 56);
-  if (i_g) std::memcpy(i_g, p->imu_i_g, 48);
-  if (i_a) std::memcpy(i_a, p->imu_i_a, 48);
-  if (S_g) std::memcpy(S_g, p->imu_S_g, 72);
-  if (X_a) std::memcpy(X_a, p->imu_X_a, 72);
+  if (const int rc = fetch(p, hs_problem::vImu)) return rc;
+  const ImuParams& ip = p->imu;
+  if (T_bs) std::memcpy(T_bs, ip.T_bs, sizeof ip.T_bs);
+  if (i_g) std::memcpy(i_g, ip.i_g, sizeof ip.i_g);
+  if (i_a) std::memcpy(i_a, ip.i_a, sizeof ip.i_a);
+  if (S_g) std::memcpy(S_g, ip.S_g, sizeof ip.S_g);
+  if (X_a) std::memcpy(X_a, ip.X_a, sizeof ip.X_a);
   return HS_OK;
-}
-
-static ImuParams pack_imu(const hs_problem* p) {
-  ImuParams ip;
-  std::memcpy(ip.T_bs, p->imu_T_bs, 56), std::memcpy(ip.i_g, p->imu_i_g, 48), std::memcpy(ip.i_a, p->imu_i_a, 48);
-  std::memcpy(ip.S_g, p->imu_S_g, 72), std::memcpy(ip.X_a, p->imu_X_a, 72);
-  return ip;
-}
-static void unpack_imu(hs_problem* p, const ImuParams& ip) {
-  std::memcpy(p->imu_T_bs, ip.T_bs, 56), std::memcpy(p->imu_i_g, ip.i_g, 48), std::memcpy(p->imu_i_a, ip.i_a, 48);
-  std::memcpy(p->imu_S_g, ip.S_g, 72), std::memcpy(p->imu_X_a, ip.X_a, 72);
 }
 
 int hs_set_inertial_jacobian(hs_problem* p, int mode) {
@@ -1153,29 +1150,27 @@ int hs_solve(hs_problem* p, int max_iterations, hs_summary* summary, hs_iteratio
   DevState& st = *p->h_state;
   const auto host_t4 = std::chrono::steady_clock::now();
   const VarTables vars = variable_tables(p);
-  if (p->want_results) {  // [cp | lm (device order) | bias_g | bias_a | gravity] -> pinned host memory, behind the last kernel
+  // The tables the device is ahead on once this solve has run: those it writes (the camera table and the IMU parameters only where it estimates
+  // their blocks) next to those it already was ahead on.
+  unsigned wrote = hs_problem::kSolved | (p->T.nc ? unsigned(hs_problem::vCam) : 0u) | (p->imu_estimated() ? unsigned(hs_problem::vImu) : 0u);
+  wrote &= max_iterations > 0 ? present_tables(vars) : 0u;
+  const unsigned ahead = p->ahead | wrote;
+  if (p->want_results) {  // those tables (the kSolved ones in any case), each into its slice of h_result: pinned host memory, behind the last kernel
     result_offsets(vars, p->result_off);
-    const size_t total = p->result_off[5];
+    const size_t total = p->result_off[vars.size()];
     if (total > p->h_result_cap) {
       if (p->h_result) (void)hipHostFree(p->h_result);
       p->h_result = nullptr, p->h_result_cap = 0;
       HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p->h_result), 2 * total * sizeof(double), hipHostMallocDefault));
       p->h_result_cap = 2 * total;
     }
-    for (int i = 0; i < 5; ++i)
-      if (vars[i].present) HIP_TRY(hipMemcpyAsync(p->h_result + p->result_off[i], vars[i].dev->p, vars[i].len * 8, hipMemcpyDeviceToHost, s));
+    for (size_t i = 0; i < vars.size(); ++i)
+      if (vars[i].present && (vars[i].bit & (ahead | hs_problem::kSolved)))
+        HIP_TRY(hipMemcpyAsync(p->h_result + p->result_off[i], vars[i].dev->p, vars[i].len * 8, hipMemcpyDeviceToHost, s));
   }
-  // Estimated cameras: the host table follows the device right here (16 doubles per camera), so hs_get_cameras, the result cache, a later
-  // upload of the camera table and the evaluation calls that send it (hs_process_tracks, hs_sample_trajectory) all see the estimate.
-  if (p->T.nc && max_iterations > 0) HIP_TRY(hipMemcpyAsync(p->cam.data(), p->d_cam.p, p->cam.size() * 8, hipMemcpyDeviceToHost, s));
-  // Estimated IMU blocks: the host copies (imu_T_bs ..) follow the device the same way, so hs_get_imu, a later upload of the parameters (hs_cost,
-  // hs_linearize, hs_reduced_system, the next hs_solve, the delta interface) and hs_snapshot see the estimate.
-  const bool imu_back = p->imu_estimated() && max_iterations > 0;
-  if (imu_back) HIP_TRY(hipMemcpyAsync(&p->imu_readback, p->d_imu.p, sizeof(ImuParams), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(&st, p->d_state.p, sizeof(st), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (imu_back) unpack_imu(p, p->imu_readback);
-  if (max_iterations > 0) p->ahead = present_tables(vars);
+  p->ahead = ahead, p->written |= wrote & hs_problem::kCalibrated;
   p->results_cached = p->want_results;  // only once every copy above has completed: a failed copy or synchronisation leaves the getters on the device path
   if (p->host_timing) {
     const auto host_t5 = std::chrono::steady_clock::now();
@@ -1238,9 +1233,7 @@ int hs_snapshot(hs_problem* p) {
     HIP_TRY(t.snap->reserve(t.len));
     HIP_TRY(hipMemcpyAsync(t.snap->p, t.dev->p, t.len * 8, hipMemcpyDeviceToDevice, p->stream));
   }
-  p->cam_snap = p->cam;  // (the host table equals the device's: hs_solve keeps it so)
-  if (p->has_imu) p->imu_snap = pack_imu(p);  // (likewise)
-  p->has_imu_snap = p->has_imu;
+  p->written = 0;
   p->has_snapshot = true;
   return HS_OK;
 }
@@ -1248,25 +1241,15 @@ int hs_snapshot(hs_problem* p) {
 int hs_restore(hs_problem* p) {
   if (!p) return HS_ERR_INVALID;
   if (!p->has_snapshot || p->changed) HS_FAIL(HS_ERR_STATE, "hs_restore without a valid hs_snapshot");
+  const VarTables vars = variable_tables(p);
+  const unsigned back = (hs_problem::kSolved | p->written) & present_tables(vars);  // (a table nothing wrote since the snapshot still equals it)
+  for (const VarTable& t : vars)  // (before the first copy: a refused restore leaves the handle as it was)
+    if ((t.bit & back) && t.len > t.snap->cap) HS_FAIL(HS_ERR_STATE, "hs_restore: a variable table is larger than its snapshot (take a new hs_snapshot)");
   p->results_cached = false;
   p->cov_valid = false;
-  const VarTables vars = variable_tables(p);
   for (const VarTable& t : vars)
-    if (t.present) HIP_TRY(hipMemcpyAsync(t.dev->p, t.snap->p, t.len * 8, hipMemcpyDeviceToDevice, p->stream));
-  p->ahead = present_tables(vars);  // (the device went back to the snapshot, the host tables did not)
-  if (p->cam != p->cam_snap && p->cam.size() == p->cam_snap.size()) {  // cameras estimated since the snapshot
-    p->cam = p->cam_snap;
-    HIP_TRY(hipMemcpyAsync(p->d_cam.p, p->cam.data(), p->cam.size() * 8, hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-  }
-  if (p->has_imu && p->has_imu_snap) {
-    const ImuParams now = pack_imu(p);
-    if (std::memcmp(&now, &p->imu_snap, sizeof(ImuParams)) != 0) {  // IMU blocks estimated since the snapshot
-      unpack_imu(p, p->imu_snap);
-      HIP_TRY(hipMemcpyAsync(p->d_imu.p, &p->imu_snap, sizeof(ImuParams), hipMemcpyHostToDevice, p->stream));
-      HIP_TRY(hipStreamSynchronize(p->stream));
-    }
-  }
+    if (t.bit & back) HIP_TRY(hipMemcpyAsync(t.dev->p, t.snap->p, t.len * 8, hipMemcpyDeviceToDevice, p->stream));
+  p->ahead |= back, p->written = 0;  // (the device went back to the snapshot, the host tables did not)
   return HS_OK;
 }
 
@@ -1521,6 +1504,7 @@ int hs_cost_function_evaluate(hs_problem* p, int type, int idx, const double* co
 /// last solve may refer to control points that the sliding window has already dropped, so prepare() is not run here.
 static int eval_tables(hs_problem* p, Tables* T, DBuf<double>* d_cp, DBuf<double>* d_cam) {
   if (p->n_cp < p->k || p->cp.empty()) HS_FAIL(HS_ERR_STATE, "hs_set_spline has not been called");
+  if (const int rc = fetch(p, hs_problem::vCp | hs_problem::vCam)) return rc;  // (the spline and the cameras as the last solve left them)
   hipStream_t s = p->stream;
   HIP_TRY(d_cp->upload(p->cp, s));
   if (!p->cam.empty()) HIP_TRY(d_cam->upload(p->cam, s));

@@ -708,7 +708,7 @@ int launch_update(hs_problem* p, bool linearize_candidate = false, bool deferred
   //  hs_solve launches k_commit once behind the last iteration)
   if (!inline_commit && !deferred_commit) k_commit<<<commit_grid(T), kBlock, 0, s>>>(T);
   if (T.nc) k_calib_commit<<<1, kBlock, 0, s>>>(T, p->d_cam.p, p->d_cam_cand.p);  // an accepted step: cam <- candidate cameras
-  if (est_i) k_imucal_commit<<<1, kBlock, 0, s>>>(T, p->d_imu.p, p->d_imu_cand.p);  // ... and imu <- candidate IMU parameters
+  if (est_i) k_imucal_commit<<<1, kBlock, 0, s>>>(T, reinterpret_cast<ImuParams*>(p->d_imu.p), p->d_imu_cand.p);  // ... and imu <- candidate IMU parameters
   HIP_TRY(hipGetLastError());
   return HS_OK;
 }

@@ -209,6 +209,10 @@ hipError_t UploadBatch::flush(hipStream_t s) {
 
 }  // namespace
 
+constexpr size_t kVarTables = 7;    // variable_tables()
+constexpr size_t kImuDoubles = 37;  // ImuParams as a table of doubles
+static_assert(sizeof(ImuParams) == kImuDoubles * sizeof(double), "ImuParams is 37 doubles without padding");
+
 struct hs_problem {
   int device = 0;
   int n_cu = 256;  // compute units of the device (hs_create): the fused build orders its chunks by how the hardware places workgroups on them
@@ -223,6 +227,11 @@ struct hs_problem {
   // Variable tables (variable_tables() below) of which the device holds values the host table does not: set by hs_solve and hs_restore, cleared per
   // table when fetch() brings it to the host or the caller's values replace it (`overwritten`) — never because something else was uploaded.
   unsigned ahead = 0;
+  // Every solve writes the kSolved tables; the camera table and the IMU parameters (kCalibrated) only where it estimates their free blocks.
+  // `written`: the kCalibrated tables whose device copy was written since hs_snapshot, by an estimating solve or an upload of new values:
+  // hs_restore takes back kSolved | written.
+  enum : unsigned { kSolved = vCp | vLm | vBias | vGravity, kCalibrated = vCam | vImu };
+  unsigned written = 0;
   void touch(unsigned what, unsigned overwritten = 0) { changed |= what, ahead &= ~overwritten, cov_valid = false; }
 
   // host tables (caller's table order)
@@ -237,7 +246,6 @@ struct hs_problem {
   std::vector<int32_t> cam_models; // hs_set_camera_models: HS_DISTORTION_* per camera, mirrored in slot 15 of `cam`; empty: every camera radial-tangential
   bool cam_estimation = false;     // hs_set_camera_estimation: hs_solve estimates the free blocks (off: it refuses a handle that has one)
   bool cam_covariance = false;     // hs_set_camera_covariance: hs_compute_covariance takes the free blocks (off: it refuses a handle that has one)
-  std::vector<double> cam_snap;    // hs_snapshot: the camera table (host copy; hs_solve keeps `cam` equal to the device table)
   int n_sensor = 0;
   std::vector<double> sensor;  // n x 8
   int n_lm = 0;
@@ -246,7 +254,7 @@ struct hs_problem {
   std::vector<double> px_stamp, px_meas, br_stamp, br_meas, pr_stamp, pr_meas, in_stamp, in_meas;
   std::vector<int32_t> px_lm, px_cam, br_lm, br_cam, pr_sensor;
   bool has_imu = false;
-  double imu_T_bs[7], imu_i_g[6], imu_i_a[6], imu_S_g[9], imu_X_a[9];
+  ImuParams imu;  // hs_set_imu: the layout of the device
   int kb = 4, n_bias = 0;
   double bias_t0 = 0, bias_dt = 1;
   std::vector<double> bias_g, bias_a;
@@ -272,7 +280,7 @@ struct hs_problem {
   // by fetch() alone, i.e. for tables the device is ahead on, whose slice cannot have changed since the copy.
   double* h_result = nullptr;
   size_t h_result_cap = 0;
-  size_t result_off[6] = {0, 0, 0, 0, 0, 0};  // slice of each variable table in h_result as of that copy ([5]: the end)
+  size_t result_off[kVarTables + 1] = {};  // slice of each variable table in h_result as of that copy (last: the end)
   bool want_results = false, results_cached = false;
   size_t vb_len = 0;                             // doubles of d_Vb / d_Vb2 in front of their zero pad (prepare())
   int zeroed_np = -1, zeroed_ncb = -1;           // layout / allocations for which the never-written parts of Sb2, Vb, yt were zeroed
@@ -293,7 +301,7 @@ struct hs_problem {
   DBuf<double> d_p_stamp, d_p_meas, d_p_rec;
   DBuf<double> d_i_stamp, d_i_meas, d_i_rec, d_bias_g, d_bias_a, d_bias_g_cand, d_bias_a_cand, d_gravity, d_gravity_cand;
   DBuf<int> d_i_first, d_i_first_bias, d_i_seg_ptr;
-  DBuf<ImuParams> d_imu;
+  DBuf<double> d_imu;  // one ImuParams (kImuDoubles; a table of doubles like every variable table)
   std::vector<int> in_order, in_first, in_first_bias, in_seg_ptr, in_bias_ptr;
   int nb_ine = 0;
   DBuf<int> d_p_sensor, d_p_first, d_p_seg_ptr;
@@ -325,7 +333,7 @@ struct hs_problem {
   DBuf<int> d_i_bias_ptr, d_bfwd_start;
   int n_split = 1;
   int rank = 0, world = 1, min_bw = 0;
-  DBuf<double> d_cp_snap, d_lm_snap;
+  DBuf<double> d_cp_snap, d_lm_snap, d_cam_snap, d_imu_snap;
   bool has_snapshot = false;
   DevState* h_state = nullptr;  // pinned
   // marginal covariances (hs_compute_covariance, kernels_covariance.hpp): allocated on first use; cov_valid until the state or a table changes
@@ -349,9 +357,6 @@ struct hs_problem {
   bool imu_covariance = false;   // hs_set_imu_covariance: hs_compute_covariance takes the free blocks (off: it refuses a handle that has one)
   bool imu_estimated() const { return ni > 0 && imu_estimation; }  // (ni: as of the last prepare())
   DBuf<ImuParams> d_imu_cand;    // candidate IMU parameters next to d_imu (k_imucal_candidate), on handles that estimate IMU blocks only
-  ImuParams imu_readback;        // hs_solve: the device parameters on their way into the host copies (imu_T_bs ..)
-  ImuParams imu_snap;            // hs_snapshot: the five blocks (host copies; hs_solve keeps them equal to the device's)
-  bool has_imu_snap = false;
   std::vector<hipEvent_t> events;
   hipStream_t side = nullptr;           // second stream: the segment partials run next to the landmark pass (independent inputs)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_irec = nullptr;
@@ -446,8 +451,9 @@ static int imu_columns(const hs_problem* p, std::vector<int>* map) {
   return n;
 }
 
-/// One variable table of the window and where its copies live. variable_tables() lists the five in the order of the read-back buffer,
-/// h_result = [cp | lm (device order) | bias_g | bias_a | gravity]; everything that handles them one by one loops over that list.
+/// One variable table of the window and where its copies live. variable_tables() lists them in the order of the read-back buffer,
+/// h_result = [cp | lm (device order) | bias_g | bias_a | gravity | cameras | IMU parameters]; everything that handles them one by one loops
+/// over that list.
 /// Invariant behind hs_problem::ahead: while a table's bit is set, its host table has the size it had at the last structural prepare() and
 /// vs.table_of_dev is the mapping of the resident device table. Every call that resizes a variable table either fetches first
 /// (hs_append_landmarks, hs_retire_landmarks) or overwrites it and thereby clears the bit; fetch() checks it rather than index past a table.
@@ -459,19 +465,21 @@ struct VarTable {
   bool present;       // part of the problem: an absent table is neither copied nor ahead
   bool device_order;  // device row d is host row vs.table_of_dev[d]
 };
-using VarTables = std::array<VarTable, 5>;
+using VarTables = std::array<VarTable, kVarTables>;
 static VarTables variable_tables(hs_problem* p) {
   const bool imu = p->has_imu, bias = imu && !p->bias_g.empty();
   return {{{hs_problem::vCp, p->cp.data(), p->cp.size(), &p->d_cp, &p->d_cp_snap, !p->cp.empty(), false},
            {hs_problem::vLm, p->lm.data(), p->lm.size(), &p->d_lm, &p->d_lm_snap, p->n_lm > 0, true},
            {hs_problem::vBias, p->bias_g.data(), p->bias_g.size(), &p->d_bias_g, &p->d_bias_g_snap, bias, false},
            {hs_problem::vBias, p->bias_a.data(), p->bias_a.size(), &p->d_bias_a, &p->d_bias_a_snap, bias, false},
-           {hs_problem::vGravity, p->gravity, 3, &p->d_gravity, &p->d_gravity_snap, imu, false}}};
+           {hs_problem::vGravity, p->gravity, 3, &p->d_gravity, &p->d_gravity_snap, imu, false},
+           {hs_problem::vCam, p->cam.data(), p->cam.size(), &p->d_cam, &p->d_cam_snap, p->n_cam > 0, false},
+           {hs_problem::vImu, reinterpret_cast<double*>(&p->imu), kImuDoubles, &p->d_imu, &p->d_imu_snap, imu, false}}};
 }
-/// The slice of every variable table in h_result: back to back in list order (off[5]: the end).
-static void result_offsets(const VarTables& v, size_t off[6]) {
+/// The slice of every variable table in h_result: back to back in list order (the last entry: the end).
+static void result_offsets(const VarTables& v, size_t off[kVarTables + 1]) {
   off[0] = 0;
-  for (int i = 0; i < 5; ++i) off[i + 1] = off[i] + v[i].len;
+  for (size_t i = 0; i < v.size(); ++i) off[i + 1] = off[i] + v[i].len;
 }
 static unsigned present_tables(const VarTables& v) {
   unsigned bits = 0;
@@ -488,7 +496,7 @@ static int fetch(hs_problem* p, unsigned mask) {
   const bool cached = p->results_cached;
   const std::vector<int>& table_of_dev = p->vs.table_of_dev;
   std::vector<double> rows;  // landmarks as the device holds them
-  for (int i = 0; i < 5; ++i) {
+  for (size_t i = 0; i < v.size(); ++i) {
     const VarTable& t = v[i];
     if (!(t.bit & mask) || !t.present) continue;
     if (t.len > t.dev->cap || (cached && t.len != p->result_off[i + 1] - p->result_off[i]) || (t.device_order && t.len != 3 * table_of_dev.size()))
@@ -499,7 +507,7 @@ static int fetch(hs_problem* p, unsigned mask) {
   }
   p->want_results |= !cached;
   if (!cached) HIP_TRY(hipStreamSynchronize(p->stream));
-  for (int i = 0; i < 5; ++i) {
+  for (size_t i = 0; i < v.size(); ++i) {
     const VarTable& t = v[i];
     if (!(t.bit & mask) || !t.present) continue;
     const double* src = cached ? p->h_result + p->result_off[i] : rows.data();
@@ -518,6 +526,7 @@ static int fetch(hs_problem* p, unsigned mask) {
 /// parameters, gravity, bias points. Sizes, indices and sort orders are those of the last structural prepare().
 static int upload_values(hs_problem* p, unsigned what) {
   hipStream_t s = p->stream;
+  p->written |= what & hs_problem::kCalibrated;  // (any upload counts, unchanged values included: the host keeps no copy of the snapshot to compare with)
   if (what & hs_problem::vCp) {
     HIP_TRY(p->d_cp.upload(p->cp, s));
     HIP_TRY(p->d_cp_cand.reserve(p->cp.size()));
@@ -547,10 +556,8 @@ static int upload_values(hs_problem* p, unsigned what) {
     HIP_TRY(p->d_lm_cand.reserve(size_t(3) * p->n_lm));
   }
   if (what & hs_problem::vImu) {
-    std::vector<ImuParams> ip(1);
-    std::memcpy(ip[0].T_bs, p->imu_T_bs, 56), std::memcpy(ip[0].i_g, p->imu_i_g, 48), std::memcpy(ip[0].i_a, p->imu_i_a, 48);
-    std::memcpy(ip[0].S_g, p->imu_S_g, 72), std::memcpy(ip[0].X_a, p->imu_X_a, 72);
-    HIP_TRY(p->d_imu.upload(ip, s));
+    const double* ip = reinterpret_cast<const double*>(&p->imu);
+    HIP_TRY(p->d_imu.upload(std::vector<double>(ip, ip + kImuDoubles), s));
   }
   if (what & hs_problem::vGravity) {
     std::vector<double> grav(p->gravity, p->gravity + 3);
@@ -1005,7 +1012,7 @@ int prepare(hs_problem* p) {
   T.n_pri = n_pri, T.p_stamp = p->d_p_stamp.p, T.p_meas = p->d_p_meas.p, T.p_sensor = p->d_p_sensor.p, T.p_first = p->d_p_first.p;
   T.p_rec = p->d_p_rec.p, T.p_seg_ptr = p->d_p_seg_ptr.p;
   T.n_ine = n_ine, T.i_stamp = p->d_i_stamp.p, T.i_meas = p->d_i_meas.p, T.i_first = p->d_i_first.p, T.i_first_bias = p->d_i_first_bias.p;
-  T.i_rec = p->d_i_rec.p, T.i_seg_ptr = p->d_i_seg_ptr.p, T.imu = p->d_imu.p;
+  T.i_rec = p->d_i_rec.p, T.i_seg_ptr = p->d_i_seg_ptr.p, T.imu = reinterpret_cast<const ImuParams*>(p->d_imu.p);
   T.bias_basis = make_basis_coef(p->kb), T.kb = p->kb, T.n_bias = p->has_imu ? p->n_bias : 0, T.bias_t0 = p->bias_t0, T.bias_dt = p->bias_dt;
   T.bias_g = p->d_bias_g.p, T.bias_a = p->d_bias_a.p, T.bias_g_cand = p->d_bias_g_cand.p, T.bias_a_cand = p->d_bias_a_cand.p;
   T.gravity = p->d_gravity.p, T.gravity_cand = p->d_gravity_cand.p, T.bias_const = p->bias_const, T.gravity_const = p->gravity_const;

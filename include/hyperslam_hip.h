@@ -170,7 +170,9 @@ int hs_set_camera_estimation(hs_problem* p, int enabled);
  * free camera coordinates of hs_set_camera_constancy. Toggling it makes a computed covariance stale. Handles without a free camera
  * coordinate are not affected by the switch. DESIGN.md section 12. */
 int hs_set_camera_covariance(hs_problem* p, int enabled);
-/* Current camera values in the layout of hs_set_cameras (n x 7, n x 4, n x 4). Each pointer may be NULL. */
+/* Current camera values in the layout of hs_set_cameras (n x 7, n x 4, n x 4): a getter of a variable table like hs_get_control_points, i.e.
+ * the estimate of the last hs_solve that estimated camera blocks (after hs_restore: the snapshot) until hs_set_cameras sends the table again.
+ * Each pointer may be NULL. */
 int hs_get_cameras(hs_problem* p, double* T_bs, double* intrinsics, double* distortion);
 /* Plain sensors (extrinsics only) used by pose-prior factors (manifold.cpp:30-33). T_bs n x 7. */
 int hs_set_sensors(hs_problem* p, int n, const double* T_bs);
@@ -216,8 +218,9 @@ int hs_set_imu_estimation(hs_problem* p, int enabled);
  * estimates both). Toggling it makes a computed covariance stale. Handles without a free IMU coordinate are not affected. DESIGN.md
  * sections 12 and 14. */
 int hs_set_imu_covariance(hs_problem* p, int enabled);
-/* Current IMU parameters in the layout of hs_set_imu: T_bs[7], i_g[6], i_a[6], S_g[9], X_a[9]. Each pointer may be NULL. HS_ERR_STATE on a
- * handle without an IMU. */
+/* Current IMU parameters in the layout of hs_set_imu: T_bs[7], i_g[6], i_a[6], S_g[9], X_a[9]: a getter of a variable table like
+ * hs_get_bias, i.e. the estimate of the last hs_solve that estimated IMU blocks (after hs_restore: the snapshot) until hs_set_imu sends the
+ * parameters again. Each pointer may be NULL. HS_ERR_STATE on a handle without an IMU. */
 int hs_get_imu(hs_problem* p, double* T_bs, double* i_g, double* i_a, double* S_g, double* X_a);
 /* Jacobian of the inertial factor. HS_INERTIAL_AS_REFERENCE (default; also HS_REFERENCE_LITERAL=1 in the environment at hs_create)
  * reproduces inertial.cpp:131-198 as written: the linear rows of the state / extrinsic-rotation columns carry I_g where the
@@ -246,11 +249,12 @@ int hs_set_inertial_residuals(hs_problem* p, int n, const double* stamps, const 
  * uploads what changed — between solves, off optimize()'s clock — and an hs_solve() that finds the tables staged uploads nothing
  * (a control-point table re-sent with new values and the same knots costs one small copy).
  * The hs_set_* functions above remain the whole-table form of the same thing; both may be mixed.
- * The variables (control points, landmarks, bias points, gravity) persist in the library table by table, in whatever order the calls
- * come: a table stays at the result of the last hs_solve (after hs_restore: at the snapshot) until the caller sends that table again
- * (hs_set_spline, hs_set_landmarks, hs_set_imu for the bias points, hs_set_gravity), and re-sending one table leaves the others where
- * they are. The getters, hs_stage and every later call that evaluates the window's residuals (hs_solve, hs_cost, hs_linearize,
- * hs_reduced_system, hs_compute_covariance) see exactly that state. */
+ * The variables (control points, landmarks, bias points, gravity, and on handles that estimate them the camera table and the IMU
+ * parameters) persist in the library table by table, in whatever order the calls come: a table stays at the result of the last hs_solve
+ * (after hs_restore: at the snapshot) until the caller sends that table again (hs_set_spline, hs_set_landmarks, hs_set_imu for the bias
+ * points and the IMU parameters, hs_set_gravity, hs_set_cameras), and re-sending one table leaves the others where they are. The getters,
+ * hs_stage and every later call that evaluates the window's residuals or its spline (hs_solve, hs_cost, hs_linearize, hs_reduced_system,
+ * hs_compute_covariance, hs_process_tracks, hs_sample_trajectory) see exactly that state. */
 /* Rows appended to the landmark table; *first_index (nullable) receives the index of the first new row (= the landmark id the residual
  * rows refer to). Replaces addLandmark (optimizer.cpp:347-358). */
 int hs_append_landmarks(hs_problem* p, int n, const double* xyz, const uint8_t* constant, int32_t* first_index);
@@ -391,8 +395,10 @@ int hs_exchange_info(hs_problem* p, int32_t* rccl_ranks, int64_t* doubles_per_li
 int hs_set_shard(hs_problem* p, int rank, int world, int min_band_blocks);
 /* Width of the block band of the reduced system in control-point blocks (max control points touched by one landmark). */
 int hs_band_blocks(hs_problem* p);
-/* Device-side copy / restore of the current point (control points, landmarks): lets a caller re-run optimize() from the
- * same window state without a host round trip (the reference's equivalent is re-creating the problem). */
+/* Device-side copy / restore of the current point, i.e. of every variable table (control points, landmarks, bias points, gravity, camera
+ * values, IMU parameters): lets a caller re-run optimize() from the same window state without a host round trip (the reference's equivalent
+ * is re-creating the problem). hs_restore brings back values, not settings: flags, switches and the camera models stay as they are now. It
+ * needs the tables of the snapshot (HS_ERR_STATE after a change that has not been prepared, or if a table has grown since). */
 int hs_snapshot(hs_problem* p);
 int hs_restore(hs_problem* p);
 

@@ -166,6 +166,79 @@ def test_hand_over(hip, oracle, build_path):
             assert abs(g.cost() - c.cost()) <= 1e-6 * c.cost()
 
 
+# The steps of test_hand_over that a getter between the solve and the next call would hide: the device holds the newest camera table (and the
+# newest spline), and set_cameras, restore + solve and process_tracks each have to start from there.
+def test_set_cameras_right_after_an_estimating_solve(hip, oracle):
+    name, w = list(sref.free_camera_windows())[0]
+    T, I, D = (np.ascontiguousarray(x) for x in (w.cam_T_bs, w.cam_intrinsics, w.cam_distortion))
+    with estimating(w, hip) as g:
+        g.solve(3)
+        assert g.lib.set_cameras(g.h, len(T), ha.problem._d(T), ha.problem._d(I), ha.problem._d(D)) == 0  # (the values the host table still holds)
+        T1, I1, D1 = g.cameras()
+        assert np.array_equal(T1, T) and np.array_equal(I1, I) and np.array_equal(D1, D)
+        wq = copy.copy(w)
+        wq.control_points, wq.landmarks, wq.cam_constant = g.control_points(), g.landmarks(), None
+        assert not np.array_equal(wq.control_points, w.control_points)
+        with ha.Problem(wq, lib=oracle) as c:
+            assert abs(g.cost() - c.cost()) <= 1e-6 * c.cost()
+
+
+SUMMARY = ("initial_cost", "final_cost", "num_iterations", "num_successful_steps", "termination", "iterations")
+
+
+def test_restore_then_solve_without_a_getter(hip):
+    name, w = list(sref.free_camera_windows())[0]
+    with estimating(w, hip) as g:
+        g.solve(3)
+        first = g.cameras()
+    assert not np.array_equal(first[0], w.cam_T_bs)
+    with estimating(w, hip) as g:
+        g.snapshot()
+        s1 = g.solve(3)
+        g.restore()
+        s2 = g.solve(3)
+        for f in SUMMARY:
+            assert s2[f] == s1[f], f
+        for a, b in zip(g.cameras(), first):
+            assert np.array_equal(a, b)
+
+
+def test_restore_refuses_a_table_larger_than_its_snapshot(hip):
+    """17 cameras (272 doubles) where the snapshot holds 2: more than the snapshot's buffer has room for, whichever way it was allocated. The
+    refusal comes before the first copy: the handle stays at the solved state."""
+    w = synthetic.small_visual(order=4, n_cp=16, n_landmarks=40, obs_pairs=3)
+    T, I, D = (np.ascontiguousarray(np.concatenate([x, np.tile(x[:1], (15, 1))])) for x in (w.cam_T_bs, w.cam_intrinsics, w.cam_distortion))
+    with ha.Problem(w, lib=hip) as g:
+        g.snapshot()
+        g.solve(3)
+        solved = g.control_points()
+        assert g.lib.set_cameras(g.h, len(T), ha.problem._d(T), ha.problem._d(I), ha.problem._d(D)) == 0
+        cost = g.cost()
+        with pytest.raises(ha.problem.HsError, match=r"\(3\).*larger than its snapshot"):
+            g.restore()
+        assert g.cost() == cost and np.array_equal(g.control_points(), solved)
+        assert not np.array_equal(solved, w.control_points)
+
+
+def test_process_tracks_right_after_an_estimating_solve(hip, oracle):
+    name, w = list(sref.free_camera_windows())[0]
+    _, wf = sref.solve(w, oracle, 3)
+    track = (w.pixel_stamps[0], w.pixels[:1], w.pixels[:1])
+    with ha.Problem(w, lib=hip) as h:
+        pre = h.process_tracks(*track)
+    with estimating(w, hip) as g:
+        g.solve(3)
+        a = g.process_tracks(*track)
+        g.control_points(), g.cameras()
+        b = g.process_tracks(*track)
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y)
+    assert not np.array_equal(a[1], pre[1]) and not np.array_equal(a[2], pre[2])  # (camera 1 is the free one; the position goes through the spline)
+    with ha.Problem(wf, lib=hip) as h:
+        e = h.process_tracks(*track)
+    assert rel(a[0], e[0]) < 1e-6 and rel(a[1], e[1]) < 1e-6
+
+
 def test_delta_append_keeps_the_estimated_cameras(hip, oracle):
     name, w = list(sref.free_camera_windows())[0]
     with estimating(w, hip) as g:

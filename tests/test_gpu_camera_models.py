@@ -337,6 +337,27 @@ def test_tags_survive(hip, oracle):
         assert g.lib.get_camera_models(g.h, ha.problem._i(m)) == 0 and list(m) == [RADTAN] * 3
 
 
+def test_restore_brings_back_values_not_models(hip, oracle):
+    """A model set after the snapshot stands after hs_restore, next to the snapshot's camera values (the estimate of the solve in between is gone)."""
+    w = cw.window((RADTAN, EQUI), order=4, n_cp=16, n_landmarks=40, obs_pairs=3, seed=7, with_priors=16)
+    w.cam_constant = ccr.flags(w, cam1="d")
+    wn = copy.copy(w)
+    wn.cam_models, wn.cam_constant = np.array([EQUI, EQUI], np.int32), None
+    with ha.Problem(w, lib=hip) as g:
+        g.set_camera_estimation(True)
+        g.snapshot()
+        g.solve(3)
+        g.set_camera_models([EQUI, EQUI])
+        g.cost()
+        g.restore()
+        assert list(g.camera_models()) == [EQUI, EQUI]
+        T, I, D = g.cameras()
+        assert np.array_equal(T, w.cam_T_bs) and np.array_equal(I, w.cam_intrinsics) and np.array_equal(D, w.cam_distortion)
+        with cmr.RefereeProblem(wn, oracle) as c, cmr.RefereeProblem(w, oracle) as c_old:
+            assert abs(c.cost() - c_old.cost()) > 1e-3 * c_old.cost()  # (the snapshot's tags would be seen)
+            assert abs(g.cost() - c.cost()) <= 1e-11 * c.cost()
+
+
 def test_refusals(hip):
     w = cw.window((EQUI, EQUI), order=4, n_cp=12, n_landmarks=10, obs_pairs=2)
     with ha.Problem(w, lib=hip) as g:

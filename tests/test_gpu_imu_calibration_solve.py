@@ -27,7 +27,7 @@ import calibration_solve_referee as csr
 import imu_calibration_referee as bref
 import imu_calibration_solve_referee as sref
 from imu_calibration_solve_referee import IMU_NAMES, imu_flags
-from test_gpu_calibration_solve import check_end_point, check_trajectory, rel
+from test_gpu_calibration_solve import SUMMARY, check_end_point, check_trajectory, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -156,6 +156,44 @@ def test_hand_over(hip, oracle, build_path):
             assert abs(g.cost() - c.cost()) <= 1e-9 * c.cost()
         assert g.solve(2)["num_iterations"] == 2  # (still estimating: the flags and the switch stand)
         assert not np.array_equal(g.imu()["T_bs"], start["T_bs"])
+
+
+# The steps of test_hand_over that a getter between the solve and the next call would hide: the device holds the newest IMU parameters.
+def test_set_imu_right_after_an_estimating_solve(hip, oracle):
+    name, w, mode, n = WINDOWS[0]
+    m = w.imu
+    start = {k: np.ascontiguousarray(np.asarray(m[k], float)).reshape(-1) for k in IMU_NAMES}
+    bg, ba = (np.ascontiguousarray(np.asarray(m[k], float)) for k in ("bias_g", "bias_a"))
+    d = ha.problem._d
+    with estimating(w, hip) as g:
+        g.solve(n)
+        assert g.lib.set_imu(g.h, *[d(start[k]) for k in IMU_NAMES], int(m["bias_order"]), float(m["bias_t0"]), float(m["bias_dt"]), bg.shape[0], d(bg), d(ba), 0) == 0
+        over = g.imu()
+        for k in IMU_NAMES:
+            assert np.array_equal(over[k], start[k]), k
+        assert not np.array_equal(g.control_points(), w.control_points)
+        with ha.Problem(oracle_window(w, g), lib=oracle) as c:
+            assert abs(g.cost() - c.cost()) <= 1e-9 * c.cost()
+
+
+def test_restore_then_solve_without_a_getter(hip):
+    name, w, mode, n = WINDOWS[0]
+    with estimating(w, hip) as g:
+        g.solve(n)
+        first = (g.imu(), g.cameras())
+    assert not np.array_equal(first[0]["T_bs"], np.asarray(w.imu["T_bs"], float).reshape(-1))
+    with estimating(w, hip) as g:
+        g.snapshot()
+        s1 = g.solve(n)
+        g.restore()
+        s2 = g.solve(n)
+        for f in SUMMARY:
+            assert s2[f] == s1[f], f
+        again = (g.imu(), g.cameras())
+    for k in IMU_NAMES:
+        assert np.array_equal(again[0][k], first[0][k]), k
+    for a, b in zip(again[1], first[1]):
+        assert np.array_equal(a, b)
 
 
 def test_delta_append_keeps_the_estimated_imu(hip, oracle):

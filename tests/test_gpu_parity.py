@@ -175,6 +175,21 @@ def test_sample_trajectory(hip, oracle):
             g.sample_trajectory([hi + 1.0])
 
 
+def test_sample_trajectory_after_a_solve_needs_no_getter(hip):
+    """The evaluation calls send the spline the last solve left on the device, whether or not a getter fetched it in between."""
+    w = synthetic.small_visual(order=4, n_cp=16, n_landmarks=80, obs_pairs=4)
+    lo, hi = w.valid_range()
+    st = np.linspace(lo, hi - 1e-6, 9)
+    with ha.Problem(w, lib=hip) as g:
+        pre = g.sample_trajectory(st)
+    with ha.Problem(w, lib=hip) as g:
+        g.solve(2)
+        a = g.sample_trajectory(st)
+        g.control_points()
+        b = g.sample_trajectory(st)
+    assert np.array_equal(a, b) and not np.array_equal(a, pre)
+
+
 @pytest.mark.parametrize("order", [4, 5, 6])
 def test_process_tracks(order, hip, oracle):
     """Pixel -> bearing conversion and stereo triangulation through the spline (abstract.cpp:197-223,250-255)."""
