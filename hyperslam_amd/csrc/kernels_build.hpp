@@ -20,7 +20,7 @@
 //   2  lane <-> (landmark, control point j'): the 6 x 3 block of W_l = sum J_p' J_l from the records of segments j' - K + 1 .. j' of that
 //      landmark (pos table: only records that contribute are visited);  lane <-> (landmark, entry): H_ll, b_l
 //   3  lane <-> (band tile (rb, cb), cb - rb < K; record stream s): P += J_p' J_p over the runs of the segments that cover both
-//      blocks; the streams of a tile sit in adjacent lanes and are combined with butterfly steps (fixed order, no LDS). Streams per
+//      blocks; the streams of a tile sit in adjacent lanes and are summed by recursive halving (fixed tree of additions, no LDS). Streams per
 //      tile: dealt per chunk from the record counts of its tiles (<= 64 band tiles; by the wave that idles during phase 1), a fixed
 //      number per diagonal offset otherwise (build_streams)
 //   4  lane <-> landmark: damped 3 x 3 Cholesky;  lane <-> (landmark, control point): Y-hat block -> LDS and HBM (k_backsub_retract)
@@ -39,7 +39,7 @@ constexpr int build_rec_stride() { return compact_record<K>() + 2; }  // LDS rec
 /// Band tiles of the chunk window that J_p'J_p touches: (rb, d = cb - rb), d < K, rb + d < bw; index = tiles of smaller d first.
 __host__ __device__ inline int band_tile_count(int bw, int k) { return k * bw - k * (k - 1) / 2; }
 HSD int band_tile_index(int rb, int d, int bw) { return d * bw - d * (d - 1) / 2 + rb; }
-/// Record streams per band tile, by diagonal offset d (adjacent lanes of one wave, combined by butterflies). A tile of offset d sees the
+/// Record streams per band tile, by diagonal offset d (adjacent lanes of one wave, summed over lane ^ 1, 2, 4, 8). A tile of offset d sees the
 /// records of K - d segments, so the diagonals get streams in proportion: greedy doubling of the most loaded diagonal (load (K - d) / ns[d])
 /// while the lanes last, at most 8 streams, never more than the diagonal before it (so that groups stay aligned to their size when the
 /// diagonals are laid out one after the other). K = 4, bw = 14: {8, 4, 4, 2} = 234 lanes, 5.5 - 8.3 records per lane where four streams for
@@ -169,6 +169,31 @@ HSD void w_ops_apply(const WOps& x, double* wacc) {
   for (int r = 0; r < 6; ++r)
 #pragma unroll
     for (int c = 0; c < 3; ++c) wacc[3 * r + c] = fma(jp[0][r], A[c], fma(jp[1][r], A[3 + c], wacc[3 * r + c]));
+}
+
+/// One level of the recursive halving of phase 3's stream sums (see there). v[0 .. N) are the values a lane of this level may hold, `own` of them
+/// valid; H = ceil(N / 2) stay with the lane whose bit is clear, the others with its partner. A lane whose bit is set first exchanges its two
+/// halves, so that BOTH lanes keep v[0 .. H) and send v[H .. N): the register index of every exchange is a compile-time constant. For an odd N
+/// entry H - 1 has no counterpart: it travels on its own, and in the upper lane — which does not keep it — the sum lands in a register
+/// behind the lane's `own` values that nobody reads (its partners of the later levels have the same lower lane bits, hence the same gap).
+/// `reach`: the lane's group has this level; the exchange itself is executed by every lane of the wave. The additions are made under the lane
+/// condition, not as `v += reach ? o : 0.0`: two instructions less per value, and the same bits, because x + 0.0 == x for every x but -0.0,
+/// which no accumulator holds: they start at +0.0, and a sum of products that starts there is -0.0 only if a product underflows to it.
+template <int N, class Xchg>
+HSD void stream_halve(double* v, bool reach, bool up, int& own, int& first, Xchg xchg) {
+  constexpr int H = (N + 1) / 2, M = N - H;
+  if (reach && up) {
+#pragma unroll
+    for (int i = 0; i < M; ++i) lane_swap(v[i], v[H + i]);
+  }
+  double o[H];
+#pragma unroll
+  for (int i = 0; i < H; ++i) o[i] = xchg(v[i < M ? H + i : i]);
+  if (reach) {
+#pragma unroll
+    for (int i = 0; i < H; ++i) v[i] += o[i];
+    first += up ? H : 0, own = up ? own - H : H;
+  }
 }
 
 constexpr int kFoldFlag = 3;  // T.join_flag[kFoldFlag] = Tables::fold_epoch once the decision workgroup of a fold-mode k_build_visual has written the state
@@ -383,7 +408,7 @@ __global__ void __launch_bounds__(kBlock, 2) k_build_visual(Tables T, int R, int
   //      landmarks were first seen late in their tracks crowds its records into two or three segments, a tile of the outer diagonal walked 30
   //      - 60 of them on two lanes, and a quarter of the chunks of configs[1] took 35 - 38 us against a median of 30 (the slowest chunk is the
   //      kernel time). Here: streams = the power of two >= records / T, at most 16, for the smallest T whose lanes fit the workgroup; the
-  //      tiles are placed by descending stream count, so every group is aligned to its size (the butterflies below need that). ----
+  //      tiles are placed by descending stream count, so every group is aligned to its size (the exchanges over lane ^ 1, 2, 4, 8 below need that). ----
   const bool dyn = nband <= 64 && !(HS_PROFILE_HOOKS && T.debug_flags < 0);  // (A/B in profiling builds, HS_DEBUG_FLAGS sign bit: the fixed rule)
   if (dyn && wave == 3) {
     int t_rb = lane, t_d = 0;
@@ -517,14 +542,13 @@ __global__ void __launch_bounds__(kBlock, 2) k_build_visual(Tables T, int R, int
   }
   const int NS = 1 << ns_lg, ns0 = 1 << (T.build_stream_lg & 3);  // (ns0: the widest groups of the fixed rule, diagonal 0)
   const int p_s = (tid - p_off) & (NS - 1);
-  // butterfly levels this wave needs (wave-uniform)
+  // levels of the stream sums this wave needs (wave-uniform)
   const bool lv2 = dyn ? __ballot(ns_lg > 1) != 0 : ns0 > 2, lv4 = dyn ? __ballot(ns_lg > 2) != 0 : ns0 > 4, lv8 = dyn && __ballot(ns_lg > 3) != 0;
   const int p_tb = band_tile_index(p_rb, p_d, bw);
-  double pacc[36], pg[6];
+  double pacc[42];  // the tile (36) and, for a diagonal tile, its share of J_p'r (6): one array, the layout of a combined tile in LDS
+  double* pg = pacc + 36;
 #pragma unroll
-  for (int e = 0; e < 36; ++e) pacc[e] = 0.0;
-#pragma unroll
-  for (int e = 0; e < 6; ++e) pg[e] = 0.0;
+  for (int e = 0; e < 42; ++e) pacc[e] = 0.0;
   if (p_lane) {
     // the runs of the <= K segments that cover both blocks of the tile, this stream's share of each; one loop over all of them
     const int o_hi = min(p_rb, nseg - 1);
@@ -557,67 +581,45 @@ __global__ void __launch_bounds__(kBlock, 2) k_build_visual(Tables T, int R, int
     }
 #undef HS_T_LOAD
   }
-  // the streams of a tile are adjacent lanes: butterfly sums, ((s0 + s1) + (s2 + s3)) + ... on every lane of the group; the groups of a wave
-  // have different sizes, so a level is exchanged by every lane and added by the lanes whose group reaches that far
+  // The streams of a tile are adjacent lanes: their sum is the fixed tree ((s0 + s1) + (s2 + s3)) + ..., evaluated by RECURSIVE HALVING. At the
+  // level of lane bit b a lane keeps one half of the values it still holds (bit clear: the lower half), hands its partner the half the partner
+  // keeps and adds the half it receives (stream_halve): the operands of every addition are the pairs of the butterfly — the sums are the
+  // same bits — but a group of NS streams exchanges 42 (1 - 1 / NS) values where the butterfly moved 42 log2(NS), and the finished values of
+  // a tile end up spread over its lanes: v[0 .. own) of a lane are the entries [first, first + own) of the tile. The groups of a wave have
+  // different sizes, so a level is exchanged by every lane and applied by the lanes whose group reaches that far.
+  int own = 42, first = 0;
   {
-    const bool t1 = NS > 1, t2 = NS > 2, t4 = NS > 4, t8 = NS > 8;
-#pragma unroll
-    for (int e = 0; e < 36; ++e) {
-      const double o = lane_xor1(pacc[e]);
-      pacc[e] += t1 ? o : 0.0;
-    }
-#pragma unroll
-    for (int e = 0; e < 6; ++e) {
-      const double o = lane_xor1(pg[e]);
-      pg[e] += t1 ? o : 0.0;
-    }
-    if (lv2) {
-#pragma unroll
-      for (int e = 0; e < 36; ++e) {
-        const double o = lane_xor2(pacc[e]);
-        pacc[e] += t2 ? o : 0.0;
-      }
-#pragma unroll
-      for (int e = 0; e < 6; ++e) {
-        const double o = lane_xor2(pg[e]);
-        pg[e] += t2 ? o : 0.0;
-      }
-    }
-    if (lv4) {
-#pragma unroll
-      for (int e = 0; e < 36; ++e) {
-        const double o = lane_xor4(pacc[e]);
-        pacc[e] += t4 ? o : 0.0;
-      }
-#pragma unroll
-      for (int e = 0; e < 6; ++e) {
-        const double o = lane_xor4(pg[e]);
-        pg[e] += t4 ? o : 0.0;
-      }
-    }
-    if (lv8) {  // (sixteen streams: lane ^ 8 = row_ror:8 inside the row of sixteen lanes)
-#pragma unroll
-      for (int e = 0; e < 36; ++e) {
-        const double o = dpp_move<0x128>(pacc[e]);
-        pacc[e] += t8 ? o : 0.0;
-      }
-#pragma unroll
-      for (int e = 0; e < 6; ++e) {
-        const double o = dpp_move<0x128>(pg[e]);
-        pg[e] += t8 ? o : 0.0;
-      }
-    }
+    const auto x1 = [](double v) { return lane_xor1(v); };
+    const auto x2 = [](double v) { return lane_xor2(v); };
+    const auto x4 = [](double v) { return lane_xor4(v); };
+    const auto x8 = [](double v) { return dpp_move<0x128>(v); };  // (lane ^ 8 = row_ror:8 inside the row of sixteen lanes)
+    stream_halve<42>(pacc, NS > 1, p_s & 1, own, first, x1);
+    if (lv2) stream_halve<21>(pacc, NS > 2, p_s & 2, own, first, x2);
+    if (lv4) stream_halve<11>(pacc, NS > 4, p_s & 4, own, first, x4);
+    if (lv8) stream_halve<6>(pacc, NS > 8, p_s & 8, own, first, x8);
   }
   HS_BSTAMP(6);
   __syncthreads();  // everybody is done with the records: the combined P tiles take their place
   HS_BSTAMP(7);
   double* Pc = recs;  // [nband][42]
-  if (p_lane && p_s == 0) {
-    double* dst = Pc + size_t(p_tb) * 42;
+  if (p_lane) {  // (own: 42 | 21 | 11, 10 | 6, 5, 4 | 3, 2, 1 for 1 | 2 | 4 | 8 | 16 streams)
+    double* dst = Pc + size_t(p_tb) * 42 + first;
 #pragma unroll
-    for (int e = 0; e < 36; e += 2) *reinterpret_cast<double2*>(dst + e) = make_double2(pacc[e], pacc[e + 1]);
+    for (int e = 0; e < 6; ++e)
+      if (e < own) dst[e] = pacc[e];
+    if (own > 6) {
 #pragma unroll
-    for (int e = 0; e < 6; e += 2) *reinterpret_cast<double2*>(dst + 36 + e) = make_double2(pg[e], pg[e + 1]);
+      for (int e = 6; e < 11; ++e)
+        if (e < own) dst[e] = pacc[e];
+    }
+    if (own > 11) {
+#pragma unroll
+      for (int e = 11; e < 21; ++e) dst[e] = pacc[e];
+    }
+    if (own > 21) {
+#pragma unroll
+      for (int e = 21; e < 42; ++e) dst[e] = pacc[e];
+    }
   }
   // ---- 4a: V = S_l H_ll S_l + D_l^2 = L L' per landmark (landmark_finish of k_landmark); the last wave, which holds the fewest tiles ----
   double lane_gmax = 0.0;  // (last wave: max |b_l| of this lane's landmark; reduced over the chunk below)
@@ -744,6 +746,8 @@ __global__ void __launch_bounds__(kBlock, 2) k_build_visual(Tables T, int R, int
         }
       }
     }
+    // (one level only: halved as in phase 3 it would be 21 exchanges, 21 register swaps and 21 additions — 105 instructions for the 126
+    //  here — with phase 6 split over the two lanes; not taken for some 60 of the kernel's 4 100 instructions per wave. A plain pair sum.)
     if (QS == 2) {  // stream 0 + stream 1 (adjacent lanes)
 #pragma unroll
       for (int e = 0; e < 36; ++e) acc[e] += lane_xor1(acc[e]);

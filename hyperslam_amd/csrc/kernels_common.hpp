@@ -32,17 +32,38 @@ HSD void give_up(DevState* st) {
 
 /// The value of lane ^ 1 / ^ 2 / ^ 4 through the DPP cross bar (vector moves; a general __shfl_xor is an LDS permute: ~80 cycles of issue per
 /// 32-bit half where these are 4). xor 4 = row_shl:4 for the lanes with bit 2 clear, row_shr:4 for the others.
+/// A lane whose source lies outside its row (the shifts) gets 0, through bound_ctrl: with the zero as the instruction's `old` operand every
+/// move was preceded by a v_mov that wrote it — half of the instructions of an exchange.
 template <int CTRL>
 HSD double dpp_move(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
   return __hiloint2double(hi, lo);
 }
 HSD double lane_xor1(double v) { return dpp_move<0xB1>(v); }  // quad_perm [1 0 3 2]
 HSD double lane_xor2(double v) { return dpp_move<0x4E>(v); }  // quad_perm [2 3 0 1]
 HSD double lane_xor4(double v) {
+#if !defined(HS_EMULATED_DEVICE)
+  // row_shl:4 into every lane, then row_shr:4 on top of it into the banks of four lanes with bit 2 set (bank_mask 0b1010): no select behind them
+  const int lo = __builtin_amdgcn_update_dpp(__builtin_amdgcn_update_dpp(0, __double2loint(v), 0x104, 0xF, 0xF, true), __double2loint(v), 0x114, 0xF, 0xA, false);
+  const int hi = __builtin_amdgcn_update_dpp(__builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x104, 0xF, 0xF, true), __double2hiint(v), 0x114, 0xF, 0xA, false);
+  return __hiloint2double(hi, lo);
+#else
   const double up = dpp_move<0x104>(v), down = dpp_move<0x114>(v);
   return (threadIdx.x & 4) ? down : up;
+#endif
+}
+/// a <-> b in the lanes that execute the statement (v_swap_b32 per half: as selects a conditional exchange of two doubles is four v_cndmask).
+HSD void lane_swap(double& a, double& b) {
+#if !defined(HS_EMULATED_DEVICE)
+  int al = __double2loint(a), ah = __double2hiint(a), bl = __double2loint(b), bh = __double2hiint(b);
+  asm volatile("v_swap_b32 %0, %1" : "+v"(al), "+v"(bl));
+  asm volatile("v_swap_b32 %0, %1" : "+v"(ah), "+v"(bh));
+  a = __hiloint2double(ah, al), b = __hiloint2double(bh, bl);
+#else
+  const double t = a;
+  a = b, b = t;
+#endif
 }
 
 /// Sum over the wave, in every lane: a butterfly over lane ^ 32, 16, 8, 4, 2, 1 — the four lower levels on the DPP cross bar (xor 8 = row_ror:8
