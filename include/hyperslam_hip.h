@@ -121,6 +121,10 @@ const char* hs_arch(void);
 /* Replaces swapState/updateState (optimizer.cpp:110-128, 286-345) + setStateManifold (backend.cpp:52-55):
  * uniform spline of order k (k control points per segment; BasisInterpolator(k-1, true)), control point j at stamp
  * t0 + j*dt. cp = n_cp x 8. cp_constant[j] != 0 freezes control point j (optimizer.cpp:323-328); may be NULL.
+ * The quaternion of every control point must have unit norm; either sign of it is accepted and kept (q and -q are the same rotation
+ * everywhere, and a solve does not change the sign a control point came with). The library neither normalises nor refuses: norms a few
+ * ulp off one (what a product of unit quaternions gives) change nothing, but a norm off by e leaves the pose exact (it is normalised) and
+ * puts a relative error of about 6 e into the rotation columns of every Jacobian (1e-6 -> 6e-6).
  * A table whose stamps are not t0 + j*dt is refused with HS_ERR_KNOTS (its own code: the one refusal a caller may want to survive,
  * see the plugin's optimize()); every other bad argument is HS_ERR_INVALID. */
 int hs_set_spline(hs_problem* p, int order, double t0, double dt, int n_cp, const double* cp, const uint8_t* cp_constant,

@@ -292,11 +292,12 @@ def perp_unit(v, rng):
     return [x / n for x in c]
 
 
-def make_case(ftype, k, rng, variant=None):
+def make_case(ftype, k, rng, variant=None, control_points=None):
     """variant: None | "u0" / "u1" (stamp at the very start / end of its segment) | "near_pi" (prior: relative rotation pi - 1e-3)
     | "small_angle" (bearing: 1e-5 rad off the measurement) | "axis" / "wide" (pixel: on the optical axis / strong distortion)
     | "identity" (inertial: I_g = I_a = I, S_g = X_a = 0, where the in-tree Jacobian is exact) | "cp_near_pi" (two consecutive control
-    points pi - 1e-2 apart: Log branch of the cumulative spline) | "gravity_pivot[_neg]" (gravity on the SphereManifold pivot axis)."""
+    points pi - 1e-2 apart: Log branch of the cumulative spline) | "gravity_pivot[_neg]" (gravity on the SphereManifold pivot axis).
+    control_points: k rows [q(4) p(3)] that replace the random walk (make_degenerate_golden.py); the random stream is drawn all the same."""
     dt = mp.mpf("0.1")
     P = {"k": k}
     q = rand_quat(rng)
@@ -309,6 +310,8 @@ def make_case(ftype, k, rng, variant=None):
             step = [(mp.pi - mp.mpf("1e-2")) * x for x in axis]
         q = qmul(q, qexp(step))
         cps.append(q + [mp.mpf(rng.uniform(lo=-1.0, hi=1.0)) for _ in range(3)] + [t_first + dt * j])
+    if control_points is not None:
+        cps = [list(c[:7]) + [t_first + dt * j] for j, c in enumerate(control_points)]
     P["cps"] = cps
     P["stamp"] = cps[(k - 1) // 2][7] + dt * mp.mpf(rng.uniform(lo=0.05, hi=0.95))
     if variant == "u0":

@@ -66,12 +66,7 @@ def test_linearization(name, w, robustify, hip, oracle):
         assert abs(g.cost() - c.cost()) <= 1e-12 * c.cost()
 
 
-@pytest.fixture(params=["fused", "records"])
-def build_path(request, monkeypatch):
-    """Both normal-equation builds of the library: the fused build (k_build_visual, default wherever a landmark's window has <= 256 tiles)
-    and the record path (HS_BUILD_PATH=records: k_linearize_visual -> k_landmark -> Gram kernels; what long feature tracks always take)."""
-    monkeypatch.setenv("HS_BUILD_PATH", request.param)
-    return request.param
+from gpu_fixtures import build_path  # noqa: E402, F401  (both normal-equation builds: the fused build and the record path)
 
 
 @pytest.mark.parametrize("name,w", list(windows()), ids=[n for n, _ in windows()])
