@@ -767,8 +767,8 @@ __global__ void __launch_bounds__(kBlock) k_border_solve(Tables T) {
   const int ti = tid / 16, tj = tid % 16;  // 16 x 16 lanes over the trailing (i, c) entries
   for (int j = 0; j < nb; ++j) {           // right-looking on the lower triangle; column j is scaled on the fly
     const double d = C[j * ld + j];
-    if (tid == 0 && !(d > 0.0)) bad = 1;
-    const double inv = 1.0 / (d > 0.0 ? d : 1.0);  // 1 / l_jj^2
+    if (tid == 0 && !pivot_ok(d)) bad = 1;
+    const double inv = 1.0 / (pivot_ok(d) ? d : 1.0);  // 1 / l_jj^2
     for (int i = j + 1 + ti; i < n1; i += 16) {
       const double lij = C[i * ld + j];
       for (int c = j + 1 + tj; c <= i && c < nb; c += 16) C[i * ld + c] = fma(-lij * inv, C[c * ld + j], C[i * ld + c]);
@@ -870,7 +870,7 @@ __global__ void __launch_bounds__(kBlock) k_border_solve_reg(Tables T) {
       const double m01 = c0[j + 1];                                // entry (j + 1, j), unscaled
       const double d1 = fma(-(m01 * inv0), m01, c1[j + 1]);        // pivot of column j + 1 after the update by column j
       const double rs1 = rsqrt_refined(d1), inv1 = rs1 * rs1;
-      if (tid == 0 && (!(d0 > 0.0) || !(d1 > 0.0))) bad = 1;
+      if (tid == 0 && (!pivot_ok(d0) || !pivot_ok(d1))) bad = 1;
       double li0[R], lc0[R], li1[R], lc1[R];
 #pragma unroll
       for (int r = Q; r < R; ++r) {
@@ -898,7 +898,7 @@ __global__ void __launch_bounds__(kBlock) k_border_solve_reg(Tables T) {
     HS_PUBLISH_COLUMN(j, cj)
     lds_barrier();
     const double d = cj[j];
-    if (tid == 0 && !(d > 0.0)) bad = 1;
+    if (tid == 0 && !pivot_ok(d)) bad = 1;
     const double rs = rsqrt_refined(d), inv = rs * rs;
     double li[R], lc[R];
 #pragma unroll

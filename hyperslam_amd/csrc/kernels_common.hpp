@@ -29,6 +29,17 @@ HSD void give_up(DevState* st) {
   st->done = 1;
 }
 
+/// The verdict of the factorisation kernels (DevState::chol_failed = 1): raised iff a pivot is not a positive FINITE number. `d > 0` alone
+/// lets +inf through (1 / sqrt of it is 0, the entries behind it NaN), and a NaN pivot is caught by it only where every pivot is tested
+/// on its own: the kernels that keep the test off their chain take the minimum of a block's pivots, and fmin drops a NaN operand.
+HSD bool pivot_ok(double d) { return d > 0.0 && d < __builtin_huge_val(); }
+/// The same verdict for the six pivots of a diagonal block from what the panel has in registers anyway, with nothing on its chain waiting:
+/// dmin, their fmin, catches a pivot <= 0 wherever it stands (a NaN beside it is the operand fmin drops). inv[a] = 1 / sqrt(d_a) by the rsq
+/// estimate + one correction step is NaN when d_a is NaN or +inf (rsq = 0, the correction multiplies it with inf), and a NaN inv[a] makes
+/// row a of the block NaN (entry * inv[a], whatever the entry), hence the next pivot, and so on down to inv[5]: one comparison of the last
+/// inverse sees a non-finite pivot anywhere in the block, the last block row of the system included, where no later pivot would.
+HSD bool block_pivots_ok(double dmin, const double (&inv)[6]) { return dmin > 0.0 && inv[5] < __builtin_huge_val(); }
+
 
 /// The value of lane ^ 1 / ^ 2 / ^ 4 through the DPP cross bar (vector moves; a general __shfl_xor is an LDS permute: ~80 cycles of issue per
 /// 32-bit half where these are 4). xor 4 = row_shl:4 for the lanes with bit 2 clear, row_shr:4 for the others.

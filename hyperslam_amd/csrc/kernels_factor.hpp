@@ -181,7 +181,7 @@ __global__ void __launch_bounds__(kCholThreads + kCholIo) k_band_factor(Tables T
       double d = U[UIDX(a, a)];
 #pragma unroll
       for (int k = 0; k < a; ++k) d = fma(-U[UIDX(k, a)], U[UIDX(k, a)], d);
-      if (!(d > 0.0)) bad = true, d = 1.0;
+      if (!pivot_ok(d)) bad = true, d = 1.0;
       // hardware estimate + two Newton steps (full double precision; the library rsqrt's scaling / special cases are not needed
       // for a positive, well-scaled pivot) and a final correction of the square root
       double r = __builtin_amdgcn_rsq(d);
@@ -623,7 +623,7 @@ __global__ void __launch_bounds__(la_threads(NCW)) k_band_factor_la(Tables T) {
         for (int k = 0; k < a; ++k) d = fma(-U[UIDX(k, a)], U[UIDX(k, a)], d);
         // A non-positive pivot is not patched on this chain: it turns the rest of the factor into NaN / inf, `fail` is raised
         // below and the step is rejected as invalid (k_decide also requires a finite model cost change).
-        dmin = a == 0 ? d : fmin(dmin, d);  // fmin drops a NaN operand only if the other is a number: checked with !(x > 0)
+        dmin = a == 0 ? d : fmin(dmin, d);  // (fmin drops a NaN operand: a non-finite pivot is seen through inv[5], block_pivots_ok)
         // 1 / sqrt(d): hardware estimate (2^-24 relative) + one third-order step, e = 1 - d y^2, y (1 + e/2 + 3 e^2/8): error ~ e^3
         const double y = __builtin_amdgcn_rsq(d);
         const double e = fma(-d * y, y, 1.0);
@@ -641,7 +641,7 @@ __global__ void __launch_bounds__(la_threads(NCW)) k_band_factor_la(Tables T) {
       }
 #pragma unroll
       for (int a = 0; a < 6; a += 2) *reinterpret_cast<double2*>(&dinv[(r & 1) * 6 + a]) = make_double2(inv[a], inv[a + 1]);  // every lane, same value
-      if (!(dmin > 0.0) && l == 0) fail = 1;
+      if (!block_pivots_ok(dmin, inv) && l == 0) fail = 1;
       if (pprof) plog[8 * r + 4] = wall_clock64();
 #pragma unroll
       for (int m = 0; m < PC; ++m) {
@@ -1016,7 +1016,7 @@ __global__ void __launch_bounds__(kWideThreads) k_band_factor_wide(Tables T) {
           U[UIDX(a, c)] = t * rs;
         }
       }
-      if (!(dmin > 0.0) && tid == 0) fail = 1;
+      if (!block_pivots_ok(dmin, inv) && tid == 0) fail = 1;
       if (tid <= ncb) {  // column tid of [U_ii | X | y]
         const int c = tid;
         double x[6];
@@ -1315,7 +1315,7 @@ __global__ void __launch_bounds__(kDenseThreads) k_dense_factor(Tables T, int n_
   auto factor_diagonal = [&](double (&t)[36], int k) {  // in place; publishes U_kk, 1 / diag and the diagonal tile of X_k
     double* ub = dscr + 32 * k;
     double* xr = xrow + (k & 1) * 6 * ldx;
-    double dmin = 1.0;
+    double dmin = 1.0, inv[6];
 #pragma unroll
     for (int a = 0; a < 6; ++a) {
       double d = t[6 * a + a];
@@ -1325,7 +1325,7 @@ __global__ void __launch_bounds__(kDenseThreads) k_dense_factor(Tables T, int n_
       const double y = __builtin_amdgcn_rsq(d);
       const double e = fma(-d * y, y, 1.0);
       const double rs = fma(y * e, fma(0.375, e, 0.5), y);
-      ub[21 + a] = rs;
+      ub[21 + a] = inv[a] = rs;
       t[6 * a + a] = d * rs;  // u_aa
 #pragma unroll
       for (int c = a + 1; c < 6; ++c) {
@@ -1335,7 +1335,7 @@ __global__ void __launch_bounds__(kDenseThreads) k_dense_factor(Tables T, int n_
         t[6 * a + c] = v * rs;
       }
     }
-    if (!(dmin > 0.0)) fail = 1;
+    if (!block_pivots_ok(dmin, inv)) fail = 1;
 #pragma unroll
     for (int a = 0; a < 6; ++a) {
 #pragma unroll
@@ -1507,7 +1507,7 @@ HSD void factor_decoupled_row(const Tables& T, const int i, const int lane) {
     double d = U[a][a];
 #pragma unroll
     for (int k = 0; k < a; ++k) d = fma(-U[k][a], U[k][a], d);
-    ok = ok && d > 0.0;
+    ok = ok && pivot_ok(d);
     const double u = sqrt(d), r = 1.0 / u;
     U[a][a] = u;
 #pragma unroll

@@ -764,7 +764,7 @@ __global__ void __launch_bounds__(kMxThreads) k_band_factor_mx(Tables T) {
       if (chain) {
 #pragma unroll
         for (int a = 0; a < 6; a += 2) *reinterpret_cast<double2*>(&dinv[(it & 1) * 8 + a]) = make_double2(inv[a], inv[a + 1]);  // every lane, same value
-        if (l == 0 && !(dmin > 0.0)) fail = 1;
+        if (l == 0 && !block_pivots_ok(dmin, inv)) fail = 1;
       }
     };
     if (cprof) clog[1] = wall_clock64();  // prologue done

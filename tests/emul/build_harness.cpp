@@ -63,8 +63,9 @@ static void run(Tables& T, int nb_vis, int R, int L, size_t lds) {
     D.Sb = Sb.data(), D.g_s = g_s.data(), D.g_full = g_full.data(), D.D2p = D2p.data(), D.gabs = gabs.data(), D.Sb2 = nullptr, D.g2 = nullptr;
     hs_emul::launch(dim3(T.sp.n_cp, 6), dim3(kAsmThreads), 0, [&] { k_assemble<K>(D, 1); });
     bool same = true;
-    for (size_t e = 0; e < nS; ++e) same &= Sb[e] == T.Sb[e];
-    for (int e = 0; e < T.np; ++e) same &= g_s[e] == T.g_s[e] && g_full[e] == T.g_full[e] && D2p[e] == T.D2p[e] && gabs[e] == T.gabs[e];
+    auto eq = [](double a, double b) { return a == b || (a != a && b != b); };  // (a window with a NaN in it — the failure path — builds NaN both ways)
+    for (size_t e = 0; e < nS; ++e) same &= eq(Sb[e], T.Sb[e]);
+    for (int e = 0; e < T.np; ++e) same &= eq(g_s[e], T.g_s[e]) && eq(g_full[e], T.g_full[e]) && eq(D2p[e], T.D2p[e]) && eq(gabs[e], T.gabs[e]);
     if (!same) {
       fprintf(stderr, "k_assemble direct mode differs from k_finalize_reduced\n");
       exit(7);
@@ -127,7 +128,8 @@ static void check_fold(const Tables& U, int nb_vis, int R, int L, size_t lds, co
 
 /// The candidate point two ways: k_update_visual (per chunk) against k_backsub_retract + k_cost_visual (per landmark / per residual).
 template <int K>
-static void run_update(Tables& T, int nb_vis, int R, int L, std::vector<double>* out, size_t build_lds, const Sizes& z, bool fold_check, bool decide) {
+static void run_update(Tables& T, int nb_vis, int R, int L, std::vector<double>* out, size_t build_lds, const Sizes& z, bool fold_check, bool decide,
+                       std::vector<double>* dec) {
   const int n_lm = T.n_lm, n_cp = T.sp.n_cp;
   std::vector<double> lm_cand_a(3 * size_t(std::max(n_lm, 1))), cp_cand_a(8 * size_t(n_cp)), cand_a(nb_vis + 1), norm_a(2 * size_t(T.n_norm_part));
   std::vector<double> lm_part_a(4 * size_t((n_lm + 3) / 4) + 4);
@@ -157,8 +159,15 @@ static void run_update(Tables& T, int nb_vis, int R, int L, std::vector<double>*
   if (decide) {  // full iteration: the trust-region decision on the fused path's partials (k_pack_decision(3): decides, commits the control points)
     std::vector<double> cp_work(T.cp, T.cp + 8 * size_t(n_cp));
     B.cp = cp_work.data();
+    const int verdict = B.st->chol_failed;  // as the factorisation left it: the decision consumes and clears it
+    const hs_iteration& rd = B.st->records[B.st->iteration];  // the record this decision writes (records[0] is the start point's: begin_iteration)
     hs_emul::launch(dim3(1), dim3(kBlock), 0, [&] { k_pack_decision(B, 3); });
     const hs_iteration& r = B.st->records[0];
+    // the state as the decision leaves it, and the point: control points (the decision's working copy) and landmarks in device order
+    dec->assign({double(verdict), double(B.st->chol_failed), double(B.st->invalid_streak), B.st->radius, double(B.st->accepted), double(B.st->done),
+                 double(B.st->termination), double(rd.step_is_valid), double(rd.step_is_successful)});
+    dec->insert(dec->end(), cp_work.begin(), cp_work.end());
+    dec->insert(dec->end(), B.lm, B.lm + 3 * size_t(n_lm));
     out->insert(out->end(), {r.cost, r.cost_change, r.gradient_max_norm, r.step_norm, r.relative_decrease, r.radius, double(r.step_is_valid), double(r.step_is_successful),
                              B.st->cost, double(B.st->accepted), double(B.st->done)});
     double dcp = 0;  // an accepted candidate was committed
@@ -177,6 +186,7 @@ int main(int argc, char** argv) {
   const int scaling_ready = hdr[10];
   const bool fold_check = (hdr[11] & 1) != 0;  // also run the decision folded into the build against k_pack_decision + build (check_fold)
   const bool full_iteration = (hdr[11] & 2) != 0;  // factor + sweeps on the built system, the update along the REAL step, the decision: one LM iteration
+  const bool failure_expected = (hdr[11] & 4) != 0;  // full iteration: a factorisation that raises chol_failed is carried through the update and the decision
   const std::vector<double> par = rd.vec<double>(3);
   const double t0 = par[0], dt = par[1], radius = par[2];
   std::vector<double> cp = rd.vec<double>(size_t(8) * n_cp);
@@ -321,17 +331,17 @@ int main(int argc, char** argv) {
     order.push_back(0);  // the inverse builders, then the sweep
     hs_emul::launch(dim3(n_wg), dim3(kCholThreads), std::max((2 * size_t(np) + 32) * sizeof(double), size_t(3 * kSbN * (kSbN + 1)) * sizeof(double)),
                     [&] { k_band_backward_sb(T, j0, j0, -1, 1, 0); }, order);
-    if (st.chol_failed) return 10;
+    if (st.chol_failed && !failure_expected) return 10;
   }
-  std::vector<double> norm_part(2), upd;
+  std::vector<double> norm_part(2), upd, dec;
   T.step_p = step_p.data(), T.delta_p = delta_p.data(), T.n_norm_part = std::max((n_cp + kBlock - 1) / kBlock, 1), T.norm_part = norm_part.data();
   const Sizes z{grpQ.size(), cost_part.size(), Y.size(), nl};
   if (k == 4)
-    run_update<4>(T, nb_vis, R, L, &upd, lds, z, fold_check, full_iteration);
+    run_update<4>(T, nb_vis, R, L, &upd, lds, z, fold_check, full_iteration, &dec);
   else if (k == 5)
-    run_update<5>(T, nb_vis, R, L, &upd, lds, z, fold_check, full_iteration);
+    run_update<5>(T, nb_vis, R, L, &upd, lds, z, fold_check, full_iteration, &dec);
   else
-    run_update<6>(T, nb_vis, R, L, &upd, lds, z, fold_check, full_iteration);
+    run_update<6>(T, nb_vis, R, L, &upd, lds, z, fold_check, full_iteration, &dec);
 
   FILE* out = fopen(argv[2], "wb");
   const int ohdr[8] = {bw, np, n_chunk, R, L, vs.y_total, int(lds), int(upd.size())};
@@ -348,6 +358,13 @@ int main(int argc, char** argv) {
   fwrite(ls_tab.data(), 8, ls_tab.size(), out);
   fwrite(scale_p.data(), 8, scale_p.size(), out);
   fwrite(upd.data(), 8, upd.size(), out);
+  if (full_iteration) {  // behind everything else: what the decision left (9 words of state, 8 n_cp control points, the landmarks back in table order)
+    std::vector<double> lm_tab_out(size_t(3) * n_lm);
+    for (int d = 0; d < n_lm; ++d)
+      for (int c = 0; c < 3; ++c) lm_tab_out[3 * vs.table_of_dev[d] + c] = dec[9 + 8 * size_t(n_cp) + 3 * d + c];
+    fwrite(dec.data(), 8, 9 + 8 * size_t(n_cp), out);
+    fwrite(lm_tab_out.data(), 8, lm_tab_out.size(), out);
+  }
   fclose(out);
   return 0;
 }

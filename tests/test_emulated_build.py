@@ -36,7 +36,7 @@ def _pack_cameras(w):
     return cam
 
 
-def run_emulated_build(exe, w, radius=1e4, R=0, L=0, scaling=None, fold=False, full=False):
+def run_emulated_build(exe, w, radius=1e4, R=0, L=0, scaling=None, fold=False, full=False, failure_expected=False):
     """Returns dict(S, g, cost, bw, n_chunk, Y, lm_scale, scale_p) of the emulated fused build on window `w`."""
     n_cp, n_lm = w.n_cp, len(w.landmarks)
     n_px, n_br = len(w.pixel_stamps), len(w.bearing_stamps)
@@ -44,7 +44,7 @@ def run_emulated_build(exe, w, radius=1e4, R=0, L=0, scaling=None, fold=False, f
     cpc = np.zeros(n_cp, i32) if w.cp_constant is None else np.asarray(w.cp_constant, i32)
     lmc = np.zeros(n_lm, i32) if w.landmark_constant is None else np.asarray(w.landmark_constant, i32)
     hdr = np.array([w.order, n_cp, n_lm, n_px, n_br, len(w.cam_T_bs), int(w.rotation_constant), int(w.translation_constant), R, L,
-                    1 if scaling is not None else 0, (1 if fold else 0) | (2 if full else 0)], i32)
+                    1 if scaling is not None else 0, (1 if fold else 0) | (2 if full else 0) | (4 if failure_expected else 0)], i32)
     parts = [hdr, np.array([w.t0, w.dt, radius], f64), np.asarray(w.control_points, f64), cpc, _pack_cameras(w), np.asarray(w.landmarks, f64), lmc,
              np.asarray(w.pixel_stamps, f64), np.asarray(w.pixels, f64), np.asarray(w.pixel_landmark, i32), np.asarray(w.pixel_camera, i32),
              np.asarray(w.bearing_stamps, f64), np.asarray(w.bearings, f64), np.asarray(w.bearing_landmark, i32), np.asarray(w.bearing_camera, i32)]
@@ -72,13 +72,19 @@ def run_emulated_build(exe, w, radius=1e4, R=0, L=0, scaling=None, fold=False, f
     Sb, g, Y = take(np_ * ncb).reshape(np_, ncb), take(np_), take(y_total)
     lm_scale, scale_p = take(3 * n_lm), take(np_)
     upd = take(n_upd)
+    decision = None
+    if full:  # what the decision left: solver state, control points, landmarks (table order)
+        d = take(9)
+        decision = dict(zip(("verdict", "chol_failed", "invalid_streak", "radius", "accepted", "done", "termination", "step_is_valid", "step_is_successful"), d))
+        decision["cp"], decision["lm"] = take(8 * n_cp).reshape(n_cp, 8), take(3 * n_lm).reshape(n_lm, 3)
+    assert off == len(raw)
     S = np.zeros((np_, np_))
     for rho in range(np_):
         c0 = 6 * (rho // 6)
         for c in range(min(ncb, np_ - c0)):
             if c0 + c >= rho:
                 S[rho, c0 + c] = S[c0 + c, rho] = Sb[rho, c]
-    return dict(S=S, g=g, cost=cost, bw=bw, n_chunk=n_chunk, R=R_, L=L_, Y=Y, lm_scale=lm_scale, scale_p=scale_p, lds=lds, upd=upd)
+    return dict(S=S, g=g, cost=cost, bw=bw, n_chunk=n_chunk, R=R_, L=L_, Y=Y, lm_scale=lm_scale, scale_p=scale_p, lds=lds, upd=upd, decision=decision)
 
 
 def _check(exe, oracle, w, radius=1e4, tol=1e-9, **kw):
@@ -176,3 +182,28 @@ def test_emulated_full_iteration_matches_oracle(harness, oracle, order, bearing,
                       (radius, "radius")):
         assert abs(got - r[name]) <= 1e-9 * max(abs(r[name]), 1e-300), (name, got, r[name])
     assert abs(st_cost - s["final_cost"]) <= 1e-9 * s["final_cost"]
+
+
+def test_emulated_decision_consumes_the_verdict(harness):
+    """The failed-factorisation path of one whole iteration: the translation of one free control point is NaN, the reduced system holds NaN in
+    that point's block rows, the band Cholesky raises DevState::chol_failed, and the decision (decide_step, kernels_update.hpp) consumes it
+    as Ceres' invalid step: verdict cleared, step neither valid nor successful, nothing accepted and nothing committed — control points and
+    landmarks bit-identical to the input —, radius halved (1e4 / 2, exact), one invalid step counted, the solve not finished.
+    The clean window reads: no verdict before or after, no invalid step counted, accepted as test_emulated_full_iteration_matches_oracle has it."""
+    w = synthetic.small_visual(order=4, n_cp=14, n_landmarks=40, obs_pairs=3)
+    d = run_emulated_build(harness, w, full=True)["decision"]
+    assert (d["verdict"], d["chol_failed"], d["invalid_streak"], d["accepted"], d["done"]) == (0, 0, 0, 1, 0)
+    assert d["step_is_valid"] == 1 and d["step_is_successful"] == 1
+    cp0 = np.array(w.control_points, float)
+    assert w.cp_constant is None  # (every control point is free)
+    cp0[w.n_cp // 2, 4:7] = np.nan  # [quaternion, translation, stamp]: the stamp stays finite (it indexes the spline)
+    w.control_points = cp0
+    d = run_emulated_build(harness, w, full=True, failure_expected=True)["decision"]
+    assert d["verdict"] == 1 and d["chol_failed"] == 0
+    assert d["step_is_valid"] == 0 and d["step_is_successful"] == 0
+    assert d["accepted"] == 0
+    assert d["radius"] == 5000.0
+    assert d["invalid_streak"] == 1
+    assert d["done"] == 0
+    assert np.array_equal(d["cp"], cp0, equal_nan=True)
+    assert np.array_equal(d["lm"], np.asarray(w.landmarks, float), equal_nan=True)

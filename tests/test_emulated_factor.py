@@ -78,8 +78,9 @@ def check_job(Ub, Ubk, yb, U, y, rows, bw, col_limit=None):
     assert np.allclose(yb[:rows], y[:rows], rtol=0, atol=1e-11)
 
 
-def run(exe, tmp_path, M, g, bw, two_ended, variant=0, f0=0, border=None):
-    """border = (S_pb, S_bb, g_b, first non-zero block row per group of two border columns): the bordered system [M S_pb; S_pb' S_bb]."""
+def run_raw(exe, tmp_path, M, g, bw, two_ended, variant=0, f0=0, border=None):
+    """One run of the harness without a verdict of its own: (returncode, failed, parts). `failed` is DevState::chol_failed as the kernels leave
+    it; parts = [m, mB, the twelve output arrays, the operands of the step outputs], None if the harness did not exit with 0."""
     n = len(M)
     P = np.arange(n)[::-1]
     src, dst = str(tmp_path / "sys.bin"), str(tmp_path / "out.bin")
@@ -95,16 +96,27 @@ def run(exe, tmp_path, M, g, bw, two_ended, variant=0, f0=0, border=None):
             for a in (border[0], border[1], border[2], scale_b, d2b):
                 f.write(np.ascontiguousarray(a, dtype="<f8").tobytes())
             f.write(np.ascontiguousarray(border[3], dtype="<i4").tobytes())
-    subprocess.check_call([exe, src, dst], timeout=180)
+    rc = subprocess.run([exe, src, dst], timeout=180).returncode
+    if rc != 0:
+        return rc, None, None
     raw = open(dst, "rb").read()
     m, mB, failed, _ = struct.unpack("=4i", raw[:16])
     v = np.frombuffer(raw[16:], dtype="<f8")
-    ncb, nU, nK = 6 * bw, n * 6 * bw, 24 * (n // 6)
-    parts, o = [], 0
+    nU, nK = n * 6 * bw, 24 * (n // 6)
+    arrays, o = [], 0
     for size in (nU, nK, n, nU, nK, n, n, n, n, 4, nb, nb):
-        parts.append(v[o:o + size])
+        arrays.append(v[o:o + size])
         o += size
-    assert failed == 0 and o == len(v)
+    assert o == len(v)
+    return rc, failed, [m, mB, arrays, (scale, g_full, d2, scale_b, d2b)]
+
+
+def run(exe, tmp_path, M, g, bw, two_ended, variant=0, f0=0, border=None):
+    """border = (S_pb, S_bb, g_b, first non-zero block row per group of two border columns): the bordered system [M S_pb; S_pb' S_bb]."""
+    n, ncb = len(M), 6 * bw
+    rc, failed, out = run_raw(exe, tmp_path, M, g, bw, two_ended, variant, f0, border)
+    assert rc == 0 and failed == 0
+    m, mB, parts, (scale, g_full, d2, scale_b, d2b) = out
     # ---- the sweeps: solution, step = -x, scaled step, and the two sums of the model cost change (decide_step adds the two ends' shares) ----
     xsol, step, delta, sums = parts[6:10]
     if border is not None:  # bordered solve: Z = U^-T S_pb, C = S_bb - Z'Z, dense Cholesky, y' = y - Z x_b, then the sweeps on y'
@@ -300,17 +312,12 @@ def test_dense_solve_mx_against_numpy(n_blk, bw, f0, n_b, harness, tmp_path):
     run(harness, tmp_path, M, g, bw, False, 6, f0, border=border)
 
 
-@pytest.mark.parametrize("n_b", [110, 64, 255, 17, 1])
-def test_dense_solve_mx_border_mode_against_numpy(n_b, harness, tmp_path):
-    """k_dense_solve_mx in border mode (Tables::dense_border, launch_factor): the border Schur complement C | h of a two-ended bordered system
-    (configs[2]: 110 unknowns) in the dense layout — padding by k_dense_border_init, entries as k_border_schur stores them — comes out as x_b
-    and nothing else is written."""
+def run_border_mode_raw(exe, tmp_path, C, h):
+    """k_dense_solve_mx in border mode on C | h without a verdict of its own: (failed, x_b)."""
+    n_b = len(h)
     rng = np.random.default_rng(977 + n_b)
-    A = rng.standard_normal((n_b, n_b + 8))
-    C = A @ A.T + np.diag(rng.uniform(0.5, 1.5, n_b))
-    h = rng.standard_normal(n_b)
     n_blk, bw = 4, 2
-    M = banded_spd(rng, n_blk, bw)
+    M = banded_spd(rng, n_blk, bw)  # (the pose part only sizes the tables: the kernel reads C | h alone)
     n = 6 * n_blk
     src, dst = str(tmp_path / "sys.bin"), str(tmp_path / "out.bin")
     P = np.arange(n)[::-1]
@@ -322,10 +329,22 @@ def test_dense_solve_mx_border_mode_against_numpy(n_b, harness, tmp_path):
         for a in (np.zeros((n, n_b)), C, h, np.ones(n_b), np.zeros(n_b)):
             f.write(np.ascontiguousarray(a, dtype="<f8").tobytes())
         f.write(np.zeros((n_b + 1) // 2 + 8, dtype="<i4").tobytes())
-    subprocess.check_call([harness, src, dst], timeout=180)
+    subprocess.check_call([exe, src, dst], timeout=180)
     raw = open(dst, "rb").read()
     _, _, failed, _ = struct.unpack("=4i", raw[:16])
-    xb = np.frombuffer(raw[16:], dtype="<f8")
+    return failed, np.frombuffer(raw[16:], dtype="<f8")
+
+
+@pytest.mark.parametrize("n_b", [110, 64, 255, 17, 1])
+def test_dense_solve_mx_border_mode_against_numpy(n_b, harness, tmp_path):
+    """k_dense_solve_mx in border mode (Tables::dense_border, launch_factor): the border Schur complement C | h of a two-ended bordered system
+    (configs[2]: 110 unknowns) in the dense layout — padding by k_dense_border_init, entries as k_border_schur stores them — comes out as x_b
+    and nothing else is written."""
+    rng = np.random.default_rng(977 + n_b)
+    A = rng.standard_normal((n_b, n_b + 8))
+    C = A @ A.T + np.diag(rng.uniform(0.5, 1.5, n_b))
+    h = rng.standard_normal(n_b)
+    failed, xb = run_border_mode_raw(harness, tmp_path, C, h)
     assert failed == 0 and len(xb) == n_b
     want = np.linalg.solve(C, h)
     assert np.allclose(xb, want, rtol=0, atol=1e-10 * max(1.0, np.abs(want).max()))
