@@ -214,7 +214,7 @@ inline bool build_chunks(const VisualStructure& vs, int n_cp, int R, int L, std:
     (*gw_ptr)[c] = int(gw_cf->size());
     if (d1 <= d0) continue;
     int d = d0;
-    while (d < d1) {  // greedy fill: as many landmarks as the two limits admit (fewest chunks; an even split of a group costs chunks)
+    while (d < d1) {  // greedy fill: as many landmarks as the two limits admit (fewest chunks; build_chunks_balanced evens them out at the same count)
       if (vs.lm_ptr[d + 1] - vs.lm_ptr[d] > R) return false;
       ch_ptr->push_back(d), gw_cf->push_back(c);
       int cnt = 0, e = d;
@@ -272,6 +272,124 @@ inline void order_chunks_for_dispatch(const VisualStructure& vs, int k, int n_cu
     for (int i = 0; i < n_pair; ++i) slot_chunk[i] = order[n_lone + i], slot_chunk[n_cu + i] = order[n - 1 - i];  // heavy w, light w + n_cu
   } else {
     for (int i = 0; i < n; ++i) slot_chunk[i] = order[i];
+  }
+  std::vector<int> out(ch_desc->size(), 0);
+  for (int w = 0; w < n; ++w) std::copy(ch_desc->begin() + 8 * slot_chunk[w], ch_desc->begin() + 8 * slot_chunk[w] + 8, out.begin() + 8 * w);
+  ch_desc->swap(out);
+}
+
+/// Chunks a greedy fill under (L landmarks, C records) makes of the landmarks [d0, d1) of one group (the fewest any split under those limits
+/// can make) and the records of its largest one; -1: a landmark with more than C records.
+inline int greedy_chunk_count(const std::vector<int>& lm_ptr, int d0, int d1, int C, int L, int* largest) {
+  int n = 0, big = 0;
+  for (int d = d0; d < d1; ++n) {
+    if (lm_ptr[d + 1] - lm_ptr[d] > C) return -1;
+    int e = d;
+    while (e < d1 && e - d < L && lm_ptr[e + 1] - lm_ptr[d] <= C) ++e;
+    big = std::max(big, lm_ptr[e] - lm_ptr[d]);
+    d = e;
+  }
+  if (largest) *largest = big;
+  return n;
+}
+
+/// Even split of the landmarks [d0, d1) of one group into k chunks (k <= d1 - d0, at least the greedy count under (L, cap)): cuts[0 .. k].
+/// Cut j goes behind the landmark whose cumulative record count is nearest to j total / k (ties: the smaller index; every chunk keeps a
+/// landmark). Landmarks of very different record counts can make such a chunk break L or cap: the group is then filled greedily under L
+/// and the smallest record limit C <= cap that needs no more than k chunks, every chunk leaving a landmark for each chunk behind it.
+/// Returns the records of the largest chunk (<= cap).
+inline int split_group_evenly(const std::vector<int>& lm_ptr, int d0, int d1, int k, int cap, int L, std::vector<int>* cuts) {
+  cuts->assign(size_t(k) + 1, d0);
+  (*cuts)[k] = d1;
+  const long long total = lm_ptr[d1] - lm_ptr[d0];
+  bool ok = true;
+  int big = 0;
+  for (int j = 1; j <= k; ++j) {
+    if (j < k) {
+      int p = (*cuts)[j - 1] + 1;
+      const int hi = d1 - (k - j);
+      auto miss = [&](int q) { return std::llabs((long long)(lm_ptr[q] - lm_ptr[d0]) * k - j * total); };
+      while (p < hi && miss(p + 1) < miss(p)) ++p;  // (the cumulative count grows with q: the first minimum is the only one)
+      (*cuts)[j] = p;
+    }
+    const int lo = (*cuts)[j - 1], up = (*cuts)[j];
+    big = std::max(big, lm_ptr[up] - lm_ptr[lo]);
+    ok = ok && up - lo <= L && lm_ptr[up] - lm_ptr[lo] <= cap;
+  }
+  if (ok) return big;
+  int C = 1;
+  for (int d = d0; d < d1; ++d) C = std::max(C, lm_ptr[d + 1] - lm_ptr[d]);
+  while (C < cap && greedy_chunk_count(lm_ptr, d0, d1, C, L, nullptr) > k) ++C;
+  big = 0;
+  for (int j = 0, d = d0; j < k; ++j) {
+    int e = d;
+    while (e < d1 - (k - 1 - j) && e - d < L && lm_ptr[e + 1] - lm_ptr[d] <= C) ++e;
+    (*cuts)[j] = d, big = std::max(big, lm_ptr[e] - lm_ptr[d]);
+    d = e;
+  }
+  return big;
+}
+
+/// descriptors of build_chunks / build_chunks_balanced: [first landmark, landmarks, first control point, first residual, residuals, chunk id, 0, 0]
+inline void fill_chunk_descriptors(const VisualStructure& vs, const std::vector<int>& ch_ptr, std::vector<int>* ch_desc) {
+  const int n = int(ch_ptr.size()) - 1;
+  ch_desc->assign(size_t(8) * std::max(n, 1), 0);
+  for (int w = 0; w < n; ++w) {
+    const int lo = ch_ptr[w], hi = ch_ptr[w + 1];
+    int* d = ch_desc->data() + 8 * w;
+    d[0] = lo, d[1] = hi - lo, d[2] = vs.lm_cfirst[lo], d[3] = vs.lm_ptr[lo], d[4] = vs.lm_ptr[hi] - vs.lm_ptr[lo], d[5] = w;
+  }
+}
+
+/// build_chunks with the landmarks of a group dealt evenly over the chunks the greedy fill makes of it (same outputs, same meaning, same chunk
+/// count: k_assemble's work lists and the partial table are sized from it). With every chunk resident at once (at most two per compute unit)
+/// a kernel over the chunks ends when the unit with the most records ends, and the greedy fill leaves full chunks beside a remainder: a group
+/// of 40 landmarks is 12 + 12 + 12 + 4 there and 10 + 10 + 10 + 10 here. No chunk has more records than the largest greedy chunk of its group.
+inline bool build_chunks_balanced(const VisualStructure& vs, int n_cp, int R, int L, std::vector<int>* ch_ptr, std::vector<int>* gw_ptr,
+                                  std::vector<int>* gw_cf, std::vector<int>* ch_desc = nullptr) {
+  int n_obs = int(vs.lm_ptr.size()) - 1;
+  while (n_obs > 0 && vs.lm_ptr[n_obs] == vs.lm_ptr[n_obs - 1]) --n_obs;  // unobserved landmarks are last in device order
+  ch_ptr->clear(), gw_cf->clear();
+  gw_ptr->assign(n_cp + 1, 0);
+  std::vector<int> cuts;
+  for (int c = 0; c < n_cp; ++c) {
+    const int d0 = std::min(vs.cf_ptr[c], n_obs), d1 = std::min(vs.cf_ptr[c + 1], n_obs);
+    (*gw_ptr)[c] = int(gw_cf->size());
+    if (d1 <= d0) continue;
+    int cap = 0;
+    const int k = greedy_chunk_count(vs.lm_ptr, d0, d1, R, L, &cap);
+    if (k < 0) return false;
+    split_group_evenly(vs.lm_ptr, d0, d1, k, cap, L, &cuts);
+    for (int j = 0; j < k; ++j) ch_ptr->push_back(cuts[j]), gw_cf->push_back(c);
+  }
+  (*gw_ptr)[n_cp] = int(gw_cf->size());
+  ch_ptr->push_back(n_obs);
+  gw_cf->push_back(0);
+  if (ch_desc) fill_chunk_descriptors(vs, *ch_ptr, ch_desc);
+  return true;
+}
+
+/// order_chunks_for_dispatch with the weight the kernels have had since their J'J phase deals its streams per chunk: every phase scales with the
+/// records and the landmarks of the chunk. Same slot scheme (workgroup w runs on compute unit w mod n_cu): with n_cu < n <= 2 n_cu the
+/// heaviest chunks get the units of their own, the rest pair heaviest (first slot) with lightest (second slot: the workgroup that lags);
+/// more than two rounds: heaviest first. Weight = records, then landmarks, then the smaller chunk id.
+inline void order_chunks_by_records(int n_cu, std::vector<int>* ch_desc, int n) {
+  if (n <= 1 || n_cu <= 0) return;
+  std::vector<int> order(n);
+  std::iota(order.begin(), order.end(), 0);
+  const int* D = ch_desc->data();
+  std::sort(order.begin(), order.end(), [&](int a, int b) {
+    if (D[8 * a + 4] != D[8 * b + 4]) return D[8 * a + 4] > D[8 * b + 4];
+    if (D[8 * a + 1] != D[8 * b + 1]) return D[8 * a + 1] > D[8 * b + 1];
+    return a < b;
+  });
+  std::vector<int> slot_chunk(n, -1);
+  if (n > n_cu && n <= 2 * n_cu) {
+    const int n_lone = 2 * n_cu - n, n_pair = n - n_cu;
+    for (int i = 0; i < n_lone; ++i) slot_chunk[n_pair + i] = order[i];
+    for (int i = 0; i < n_pair; ++i) slot_chunk[i] = order[n_lone + i], slot_chunk[n_cu + i] = order[n - 1 - i];
+  } else {
+    slot_chunk = order;
   }
   std::vector<int> out(ch_desc->size(), 0);
   for (int w = 0; w < n; ++w) std::copy(ch_desc->begin() + 8 * slot_chunk[w], ch_desc->begin() + 8 * slot_chunk[w] + 8, out.begin() + 8 * w);

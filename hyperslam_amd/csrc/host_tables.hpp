@@ -762,8 +762,21 @@ int prepare(hs_problem* p) {
       p->fused = choose_build_geometry(k, R0, L0, size_t(overridden ? 156 : 79) * 1024, size_t(156) * 1024, lds_bytes, &p->build_R, &p->build_L) &&
                  build_chunks(vs, p->n_cp, p->build_R, p->build_L, &p->h_ch_ptr, &p->h_gw_ptr, &p->h_gw_cf, &p->h_ch_desc);
       p->build_lds = p->fused ? lds_bytes(p->build_R, p->build_L) : 0;
-      if (p->fused && !std::getenv("HS_BUILD_ORDER"))  // (HS_BUILD_ORDER=table: chunks in table order, measurement switch)
-        order_chunks_for_dispatch(vs, k, p->n_cu, &p->h_ch_desc, int(p->h_ch_ptr.size()) - 1);
+      // Chunks that are all resident at once (at most two per compute unit): the kernels end with the unit that has the most records, so the
+      // landmarks of a group are dealt evenly over its chunks (same chunk count) and the chunks are paired on the units by their records.
+      // More rounds than that: the hardware hands the next chunk to the slot that frees first and the small remainder chunks of the greedy
+      // fill, dispatched last, fill the tail — the even split measured 2 % SLOWER there (configs[3], configs[2]: DESIGN 5.6).
+      // HS_BUILD_SPLIT=greedy / =even: one rule everywhere (measurement switch, like HS_BUILD_ORDER).
+      const char* split = std::getenv("HS_BUILD_SPLIT");
+      const int n_chunk = int(p->h_ch_ptr.size()) - 1;
+      const bool even = p->fused && (split ? std::strcmp(split, "even") == 0 : n_chunk <= 2 * p->n_cu);
+      if (even) build_chunks_balanced(vs, p->n_cp, p->build_R, p->build_L, &p->h_ch_ptr, &p->h_gw_ptr, &p->h_gw_cf, &p->h_ch_desc);
+      if (p->fused && !std::getenv("HS_BUILD_ORDER")) {  // (HS_BUILD_ORDER=table: chunks in table order, measurement switch)
+        if (even)
+          order_chunks_by_records(p->n_cu, &p->h_ch_desc, n_chunk);
+        else
+          order_chunks_for_dispatch(vs, k, p->n_cu, &p->h_ch_desc, n_chunk);
+      }
     }
     if (!p->fused) {
       HIP_TRY(p->d_v_rec.reserve(size_t(n_vis) * (8 + 12 * k) + 1));

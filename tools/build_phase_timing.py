@@ -108,5 +108,16 @@ sl = [i for i in np.where(slow)[0] if i in part]
 print("  slow chunk vs its CU partner, medians: duration %.2f / %.2f  start %.2f / %.2f  records %d / %d" % (np.median(dur[sl]), np.median([dur[part[i]] for i in sl]),
       np.median(start[sl]), np.median([start[part[i]] for i in sl]), np.median(t[sl, 0, 13]), np.median([t[part[i], 0, 13] for i in sl])))
 print("  stamps of the slow chunk minus its partner's, median per stamp (us):", " ".join(f"{x:5.2f}" for x in np.median([(t[i, :, :13].max(axis=0) - t[part[i], :, :13].max(axis=0)) * 0.01 for i in sl], axis=0)))
+# first and second workgroup of the shared CUs (by workgroup index: w and w + n_cu), and the workgroups with a CU of their own
+if pairs:
+    fa, sb = np.array([a for a, b in pairs]), np.array([b for a, b in pairs])
+    rec = t[:, 0, 13]
+    print("shared CUs: end of the first workgroup (median, max) %.2f %.2f  of the second %.2f %.2f  second minus first (median, max) %.2f %.2f" %
+          (np.median(end[fa]), end[fa].max(), np.median(end[sb]), end[sb].max(), np.median(end[sb] - end[fa]), (end[sb] - end[fa]).max()))
+    print("shared CUs: records of the first + second workgroup (min, median, max)", int((rec[fa] + rec[sb]).min()), float(np.median(rec[fa] + rec[sb])),
+          int((rec[fa] + rec[sb]).max()), " second workgroups ending > 2 us behind their partner:", int((end[sb] - end[fa] > 2.0).sum()), "of", len(pairs))
+if lone:
+    li = np.array([int(np.where(key == k_)[0][0]) for k_ in uniq[cnt == 1]])
+    print("lone workgroups: end (median, max) %.2f %.2f  records (min, max) %d %d" % (np.median(end[li]), end[li].max(), t[li, 0, 13].min(), t[li, 0, 13].max()))
 nsl = [i for i in np.where(~slow)[0] if i in part and not slow[part[i]]]
 print("  pairs without a slow chunk:", len(nsl) // 2, " workgroup indices (mod 256) histogram by 32:", np.bincount((wgid[nsl] % 256) // 32, minlength=8) // 2)
